@@ -18,9 +18,20 @@ is used only for the start/stop barrier and the max-over-ranks time.  Ranks
 come from torchrun's environment, or -- `--gpus N` with no WORLD_SIZE set --
 bench.py starts its own N rank processes (self_launch: child processes with
 RANK/LOCAL_RANK/WORLD_SIZE/MASTER_*; the parent never touches the GPU).
-Which curve a line is: config.curve.  The weak cfg2 line also carries the
-strong configs[4] split measured in the same job ("configs4_strong": 524 288
-x 1 KiB over the same ranks), so a 1/2/4/8 sweep yields both curves.
+Which curve a line is: config.curve.
+
+A plain run (`--gpus N --steps K --warmup W`) sets up, runs W untimed and K
+timed steps and prints the result line.  `--full` adds what takes runs of its
+own: the CPU baseline (--cpu-seconds) and, on the weak cfg2 line, the strong
+configs[4] split measured in the same job ("configs4_strong": 524 288 x 1 KiB
+over the same ranks, with its 2/4/8-GPU shard projection at N = 1), so a
+1/2/4/8 `--full` sweep yields both curves.
+
+`--dump-outputs DIR`: after the timed steps each rank writes the payload the
+last timed step crypted (that step's batch, as a caller would read it back) to
+DIR/payload.npy (rank r > 0: payload_rank<r>.npy) as float32; batches above
+DUMP_MAX_BYTES are cut to a fixed, seeded sample of whole sessions.  Inputs
+are seeded, so equal arguments give equal files.
 
 HBM honesty: each rank rotates over R distinct batches (distinct sessions,
 states and payload buffers) totalling >= --footprint-mib (default 640 MiB, i.e.
@@ -85,6 +96,28 @@ def rotation_batches(S: int, L: int, footprint_mib: int) -> int:
 def shard_first(rank: int, R: int, S: int) -> int:
     """Global id of rank r's first session: ranks own disjoint session ranges."""
     return rank * R * S
+
+
+DUMP_MAX_BYTES = 32 << 20      # --dump-outputs: float32 bytes per rank's array
+
+
+def dump_sessions(S: int, L: int, max_bytes: int = DUMP_MAX_BYTES):
+    """The sessions of a batch that --dump-outputs writes: None for all of
+    them, or -- where S x L float32 values exceed max_bytes -- a fixed, seeded
+    sample of whole sessions (sorted indices into the batch)."""
+    k = max(1, max_bytes // (4 * L))
+    if k >= S:
+        return None
+    return np.sort(np.random.default_rng(2024).choice(S, k, replace=False))
+
+
+def dump_outputs(dirname, rank: int, out: np.ndarray) -> Path:
+    """Write one rank's last-step output as DIR/payload.npy (float32)."""
+    d = Path(dirname)
+    d.mkdir(parents=True, exist_ok=True)
+    p = d / ("payload.npy" if rank == 0 else f"payload_rank{rank}.npy")
+    np.save(p, np.ascontiguousarray(out, dtype=np.float32))
+    return p
 
 
 # ------------------------------------------------------------------ GPU leg
@@ -173,6 +206,18 @@ class GpuRunner:
 
     def check(self) -> None:
         self.ctx.sync(self.stream)
+
+    def last_output(self, i: int) -> np.ndarray:
+        """What step i left in the payload buffer: batch i % R, session-major
+        [S][L] bytes (every slot mode crypts the batch's own sessions in
+        place), on the host; large batches: the dump_sessions sample."""
+        b = i % self.R
+        n = self.S * self.L
+        out = self.payload[b * n:(b + 1) * n].view(self.S, self.L)
+        pick = dump_sessions(self.S, self.L)
+        if pick is not None:
+            out = out[self.torch.from_numpy(pick).to(out.device)]
+        return out.cpu().numpy()
 
     def close(self) -> None:
         """Free the batches and the arena (before the companion measurement)."""
@@ -274,6 +319,8 @@ def run_bench(args, ws, rank, local, backend="nccl", make_runner=None, own_pg=Tr
     elapsed = time.perf_counter() - t0
     kern_ms = runner.segment_ms(args.steps, args.event_every, marks)
     runner.check()
+    if getattr(args, "dump_outputs", None):
+        dump_outputs(args.dump_outputs, rank, runner.last_output(args.warmup + args.steps - 1))
 
     t = torch.tensor([elapsed, statistics.mean(kern_ms)], dtype=torch.float64, device=dev)
     if ws > 1:
@@ -297,7 +344,7 @@ def run_bench(args, ws, rank, local, backend="nccl", make_runner=None, own_pg=Tr
                            "kernel_avg_us": round(k * 1e3, 3),
                            "achieved_gbs": round(B / (k * 1e-3) / 1e9, 2)}
                           for r, (e, k) in enumerate(per_rank)]
-        if args.cpu_seconds > 0 and ws == 1 and make_runner is None:
+        if getattr(args, "full", False) and args.cpu_seconds > 0 and ws == 1 and make_runner is None:
             res["cpu_baseline"] = cpu_baseline(args, S, L)
         else:
             res["cpu_baseline"] = None
@@ -353,7 +400,7 @@ def build_result(args, ws, S, L, R, tmax, kern_avg_ms, kern_ms, total_payload):
                    "parallelism": f"shard{ws} (sessions split across GPUs, no collective)",
                    "curve": (f"strong: {args.workload}'s {S * ws} sessions split over {ws} GPU(s)" if args.strong
                              else f"weak: {args.workload} per GPU on each of {ws} GPU(s); the strong configs[4] "
-                                  f"split is 'configs4_strong' (or --workload cfg5 --strong)"),
+                                  f"split is 'configs4_strong' with --full (or --workload cfg5 --strong)"),
                    "slot_ids": getattr(args, "ids", "range")},
         "roofline": {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
                      "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5),
@@ -851,8 +898,14 @@ def parse(argv=None):
                    help="the workload's sessions are the whole job, split across ranks (BASELINE configs[4])")
     p.add_argument("--footprint-mib", type=int, default=640,
                    help="rotate over distinct batches totalling this many MiB per GPU (0 = one batch)")
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the headline figure does not need: the CPU baseline (--cpu-seconds) "
+                        "and, on the weak cfg2 line, the strong configs[4] companion with its shard projection")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write the payload the last timed step crypted to DIR/payload.npy "
+                        "(float32; rank r > 0: payload_rank<r>.npy; large batches: a fixed seeded sample of sessions)")
     p.add_argument("--cpu-seconds", type=float, default=10.0,
-                   help="CPU baseline time budget on rank 0 at N=1 (0 disables)")
+                   help="with --full (or --ksa / --frame): CPU baseline time budget on rank 0 at N=1 (0 disables)")
     p.add_argument("--cpu-threads", type=int, default=0,
                    help="cap on CPU-baseline threads (0 = every core in the affinity mask)")
     p.add_argument("--ids", choices=["range", "grouped", "declared", "scattered"], default="range",
@@ -871,7 +924,7 @@ def parse(argv=None):
     p.add_argument("--zero-copy", action="store_true",
                    help="with --host-inclusive: run the kernels directly on the pinned host buffer")
     p.add_argument("--companion-workload", choices=sorted(CONFIG_SHAPES) + ["none"], default="cfg5",
-                   help="with the default weak cfg2 line: also measure this workload split over the same ranks "
+                   help="with --full on the default weak cfg2 line: also measure this workload split over the same ranks "
                         "(strong scaling, BASELINE configs[4]) as 'configs4_strong'; none disables")
     p.add_argument("--no-shard-projection", dest="shard_projection", action="store_false",
                    help="N=1 only: skip timing the companion's 2/4/8-GPU shards on this GPU "
@@ -956,6 +1009,7 @@ def companion_strong(args, ws, rank, local, backend="nccl", make_runner=None):
     launches)."""
     c = argparse.Namespace(**vars(args))
     c.workload, c.strong, c.cpu_seconds, c.ids = args.companion_workload, True, 0.0, "range"
+    c.dump_outputs = None          # the dump is the headline path's
     c.steps = max(args.steps, args.companion_steps)
     c.warmup = max(args.warmup, args.companion_warmup)
     res, runner = run_bench(c, ws, rank, local, backend, make_runner, own_pg=False)
@@ -1041,8 +1095,8 @@ def rank_main(args, backend="nccl", make_runner=None):
     if hasattr(runner, "close"):
         runner.close()
     del runner
-    if args.companion_workload != "none" and not args.strong and args.workload in COMPANION_BASES \
-            and getattr(args, "ids", "range") == "range":
+    if getattr(args, "full", False) and args.companion_workload != "none" and not args.strong \
+            and args.workload in COMPANION_BASES and getattr(args, "ids", "range") == "range":
         comp = companion_strong(args, ws, rank, local, backend, make_runner)
         if rank == 0:
             res["configs4_strong"] = comp

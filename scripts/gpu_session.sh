@@ -27,7 +27,7 @@ timeout -k 10 180 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smok
 rc=$?; cat $OUT/smoke.log | tail -2; stop_on_fault $rc smoke
 
 for wl in $WLS; do
-  timeout -k 10 300 python bench.py --workload $wl --steps 200 --warmup 20 --cpu-seconds 6 \
+  timeout -k 10 300 python bench.py --full --workload $wl --steps 200 --warmup 20 --cpu-seconds 6 \
       > $OUT/bench_$wl.json 2> $OUT/bench_$wl.err
   rc=$?; cat $OUT/bench_$wl.json; stop_on_fault $rc bench-$wl
 done

@@ -19,7 +19,7 @@ if [ -z "${VAL_SKIP_TESTS:-}" ]; then
   TAILN=4 step gpu_tests 1500 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread -p no:cacheprovider
   step smoke 200 python -c "import __graft_entry__ as g; g.smoke()"
 fi
-step bench_default 300 python bench.py --steps 20 --warmup 5
+step bench_default 300 python bench.py --full --steps 20 --warmup 5
 step bench_default_200 300 python bench.py --steps 200 --warmup 20 --cpu-seconds 0
 step bench_cfg2_grouped 300 python bench.py --ids grouped --steps 200 --warmup 20 --cpu-seconds 0 --companion-workload none
 step bench_cfg5 300 python bench.py --workload cfg5 --steps 200 --warmup 120 --cpu-seconds 0

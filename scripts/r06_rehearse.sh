@@ -30,9 +30,9 @@ assert "rehearsal" in d["config"] and d["config"]["dist_backend"] == "gloo"
 print(f"[check {n}] ok: value {d['value']} GiB/s, companion {c['value']} GiB/s (shared GPU: shape only)")
 EOF
 }
-step self_launch_2 400 python bench.py --gpus 2 --steps 20 --warmup 5 --rehearse-one-gpu
+step self_launch_2 400 python bench.py --gpus 2 --full --steps 20 --warmup 5 --rehearse-one-gpu
 check self_launch_2 2
 step torchrun_4 500 python -m torch.distributed.run --nnodes=1 --nproc-per-node 4 --master-addr 127.0.0.1 \
-    --master-port 29517 bench.py --gpus 4 --steps 20 --warmup 5 --rehearse-one-gpu
+    --master-port 29517 bench.py --gpus 4 --full --steps 20 --warmup 5 --rehearse-one-gpu
 check torchrun_4 4
 echo rehearse done

@@ -36,6 +36,15 @@ class OracleRunner:
     def check(self):
         pass
 
+    def last_output(self, i):
+        """bench.GpuRunner.last_output: batch i % R of the payload, [S][L]."""
+        import bench
+        b = i % self.R
+        n = self.S * self.L
+        out = self.w.payload[b * n:(b + 1) * n].reshape(self.S, self.L)
+        pick = bench.dump_sessions(self.S, self.L)
+        return out if pick is None else out[pick]
+
     # bench.GpuRunner's timing interface: events made before the timed
     # region, launches, then per-segment ms per step
     def make_events(self, k, every=16):

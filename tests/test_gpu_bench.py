@@ -38,3 +38,34 @@ def test_bench_runner_matches_oracle(built, ids, S):
                                f"(sessions {sorted(set((bad[:64] // L).tolist()))[:8]})")
     finally:
         run.close()
+
+
+@pytest.mark.gpu
+def test_dump_outputs_is_the_last_timed_steps_batch(built, tmp_path, monkeypatch):
+    """--dump-outputs: after W warmup and K timed steps over R rotating batches
+    the file holds batch (W + K - 1) % R exactly as the oracle leaves it
+    (300 sessions: a ragged last group), as float32 [S][L]; K really is the
+    number of timed steps and the line carries ms_per_step."""
+    import bench
+    from oracle_runner import OracleRunner
+    S, L, W, K = 300, 64, 1, 3
+    monkeypatch.setitem(bench.CONFIG_SHAPES, "tiny300", (S, L))
+    monkeypatch.setitem(bench.CONFIG_TEXT, "tiny300", "300 sessions x 64 B (test shape)")
+    args = bench.parse(["--steps", str(K), "--warmup", str(W), "--footprint-mib", "1",
+                        "--dump-outputs", str(tmp_path / "out")])
+    args.workload = "tiny300"
+    res, run = bench.run_bench(args, 1, 0, 0)
+    try:
+        R = run.R
+        assert R > W + K                       # every step its own batch: the last one is batch W + K - 1
+        ref = OracleRunner(S, L, R, 0)
+        for i in range(W + K):
+            ref.step(i)
+        got = np.load(tmp_path / "out" / "payload.npy")
+        assert got.dtype == np.float32 and got.shape == (S, L)
+        assert np.array_equal(got, ref.last_output(W + K - 1).astype(np.float32))
+        assert np.array_equal(run.payload.cpu().numpy(), ref.w.payload)      # K timed steps, no more
+        assert res["steps"] == K and res["ms_per_step"] > 0
+        assert res["cpu_baseline"] is None and "configs4_strong" not in res
+    finally:
+        run.close()

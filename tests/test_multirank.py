@@ -121,10 +121,10 @@ def test_self_launch_two_ranks(capsys):
     the two rank processes itself (here tests/bench_child_cpu.py: the same
     rank_main over gloo with the oracle runner) and relays rank 0's line,
     which names the weak curve, the world size the process group saw, one
-    per_gpu entry per rank, and the strong configs[4]-style companion split
-    over the same ranks."""
+    per_gpu entry per rank, and -- with --full -- the strong configs[4]-style
+    companion split over the same ranks."""
     import bench
-    argv = ["--gpus", "2", "--workload", "tiny", "--steps", "3", "--warmup", "1", "--footprint-mib", "0",
+    argv = ["--gpus", "2", "--full", "--workload", "tiny", "--steps", "3", "--warmup", "1", "--footprint-mib", "0",
             "--cpu-seconds", "0", "--companion-workload", "tiny2", "--companion-steps", "2",
             "--companion-warmup", "1"]
     rc = bench.self_launch(argv, 2, entry=ROOT / "tests" / "bench_child_cpu.py", timeout=240)
@@ -177,6 +177,66 @@ def test_self_launch_reports_a_failing_rank(capsys):
     argv = ["--gpus", "2", "--workload", "no-such-shape"]
     rc = bench.self_launch(argv, 2, entry=ROOT / "tests" / "bench_child_cpu.py", timeout=100)
     assert rc != 0
+
+
+def _one_rank(monkeypatch, *extra):
+    """bench.rank_main as the only rank, on the CPU with the oracle runner."""
+    import bench
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setitem(bench.CONFIG_SHAPES, "tiny", (256, 64))
+    monkeypatch.setitem(bench.CONFIG_TEXT, "tiny", "256 sessions x 64 B (test shape)")
+    monkeypatch.setitem(bench.CONFIG_SHAPES, "tiny2", (512, 64))
+    monkeypatch.setitem(bench.CONFIG_TEXT, "tiny2", "512 sessions x 64 B job (test shape)")
+    monkeypatch.setattr(bench, "COMPANION_BASES", {"tiny"})
+    args = bench.parse(["--steps", "3", "--warmup", "1", "--footprint-mib", "1", "--cpu-seconds", "0",
+                        "--companion-workload", "tiny2", "--companion-steps", "2", "--companion-warmup", "1", *extra])
+    args.workload = "tiny"
+    return bench.rank_main(args, backend="gloo", make_runner=OracleRunner)
+
+
+def test_plain_run_measures_the_headline_only(monkeypatch, capsys):
+    """Without --full the line has the headline fields and neither the CPU
+    baseline nor the configs[4] companion; --full brings the companion back."""
+    res = _one_rank(monkeypatch)
+    line = json.loads(capsys.readouterr().out.splitlines()[-1])
+    assert line == json.loads(json.dumps(res))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in res
+    assert res["steps"] == 3 and res["ms_per_step"] > 0 and res["higher_is_better"] is True
+    assert res["cpu_baseline"] is None and "configs4_strong" not in res
+    full = _one_rank(monkeypatch, "--full")
+    assert full["configs4_strong"]["scaling"] == "strong"
+    assert full["metric"] == res["metric"] and full["unit"] == res["unit"]
+
+
+def test_dump_outputs_writes_the_last_timed_steps_batch(monkeypatch, tmp_path):
+    """--dump-outputs DIR: payload.npy is the batch the last timed step
+    crypted, float32 [S][L]; the same arguments give the same bytes, and the
+    --full companion leaves the file alone."""
+    a, b = tmp_path / "a", tmp_path / "b"
+    _one_rank(monkeypatch, "--dump-outputs", str(a))
+    _one_rank(monkeypatch, "--dump-outputs", str(b), "--full")
+    got = np.load(a / "payload.npy")
+    assert got.dtype == np.float32 and got.shape == (256, 64)
+    assert [p.name for p in b.iterdir()] == ["payload.npy"]
+    assert (a / "payload.npy").read_bytes() == (b / "payload.npy").read_bytes()
+    import bench
+    R = bench.rotation_batches(256, 64, 1)
+    assert R > 4                                    # step 3 (the last: 1 warmup + 3 timed) is batch 3
+    ref = OracleRunner(256, 64, R, 0)
+    for i in range(4):
+        ref.step(i)
+    assert np.array_equal(got, ref.w.payload[3 * 256 * 64:4 * 256 * 64].reshape(256, 64).astype(np.float32))
+
+
+def test_dump_sessions_samples_large_batches_only():
+    import bench
+    assert bench.dump_sessions(4096, 1024) is None              # cfg2: 16 MiB as float32, whole
+    pick = bench.dump_sessions(524288, 1024)                    # cfg5: 2 GiB as float32 -> 8192 sessions
+    assert pick.size == 8192 and pick.size * 1024 * 4 <= bench.DUMP_MAX_BYTES
+    assert np.all(np.diff(pick) > 0) and 0 <= pick[0] and pick[-1] < 524288
+    assert np.array_equal(pick, bench.dump_sessions(524288, 1024))
 
 
 def test_usable_cpus_caps_affinity_by_quota(monkeypatch):
