@@ -308,6 +308,65 @@ int zrc4_set_state(zrc4_ctx *ctx, uint32_t id, const uint8_t sbox[256],
 int zrc4_get_states(zrc4_ctx *ctx, uint32_t first_slot, uint32_t n,
                     uint8_t *sbox, uint8_t *x, uint8_t *y);
 
+/* Batched device-side export / import of states as RECORDS, and slot-to-slot
+ * copy (checkpoint and restore of a shard, session migration between
+ * contexts, arena compaction, copying an RC4Encryption value).
+ *
+ * Record i is sbox[256 i + k] = S[k] (k = 0..255) and xy[i] = x | y << 8: the
+ * values zrc4_get_states returns and the arena's own x/y word.  sbox and xy
+ * are DEVICE pointers (sbox 16-byte aligned, xy 2-byte aligned, else
+ * ZRC4_ERR_INVALID_ARG); the calls are stream-ordered and asynchronous.
+ *
+ * Entry i names slot ids[i], or first_slot + i when ids is NULL (then
+ * first_slot + n <= capacity, else ZRC4_ERR_SLOT_RANGE with nothing
+ * launched).  n == 0 returns ZRC4_OK.  An entry with ids[i] ==
+ * ZRC4_IDLE_SLOT is skipped: an export leaves its record untouched.  Any
+ * other id >= capacity is skipped too and reported by zrc4_sync as
+ * ZRC4_ERR_SLOT_RANGE; the rest of the call runs.
+ *
+ * zrc4_import_states changes only the bytes of the slots it names: every
+ * other slot of a touched group keeps its state.  A slot named twice ends
+ * with unspecified bytes of its two records; no other slot is affected.  With
+ * ids == NULL a partly covered group is read, merged and written back as a
+ * whole image, so the rule on concurrent streams and disjoint groups (top of
+ * this file) applies as for every call that moves a group.
+ *
+ * zrc4_copy_states copies entry i's source slot (src_ids / src_first in src)
+ * to its destination slot (dst_ids / dst_first in dst).  Both contexts must
+ * be on the same device (else ZRC4_ERR_INVALID_ARG); dst == src is allowed.
+ * Every source is read before any destination is written, so overlapping
+ * ranges and permutations are well defined.  An entry is skipped when either
+ * of its ids is skipped (a source id >= capacity is latched on src, a
+ * destination id on dst).  The records pass through a device scratch of
+ * n * 258 bytes owned by dst, grown on demand (the stream is waited for
+ * first) and kept; if it cannot be had: ZRC4_ERR_OUT_OF_MEMORY, nothing
+ * launched.  Copies into one destination context share that scratch: a copy
+ * issued on another stream than the previous one first waits (on the device)
+ * for the previous copy to finish.
+ *
+ * zrc4_set_states is the blocking host mirror of zrc4_get_states: host
+ * pointers, slots [first_slot, first_slot + n).
+ *
+ * These calls move the DEVICE state as it stands.  A slot driven through a
+ * keystream reservoir (zrc4_ks) runs ahead of its stream position by the
+ * bytes its ring holds, so such slots are copied with zrc4_ks_copy, which
+ * moves the buffered keystream along (and uses zrc4_copy_states underneath
+ * when both reservoirs' contexts are on one device).
+ *
+ * Between two GPUs: zrc4_export_states on the source context, a peer copy of
+ * the records (hipMemcpyPeerAsync), zrc4_import_states on the other context
+ * ("Moving sessions"). */
+int zrc4_export_states(zrc4_ctx *ctx, const uint32_t *ids, uint32_t first_slot,
+                       uint32_t n, uint8_t *sbox, uint16_t *xy, void *stream);
+int zrc4_import_states(zrc4_ctx *ctx, const uint32_t *ids, uint32_t first_slot,
+                       uint32_t n, const uint8_t *sbox, const uint16_t *xy,
+                       void *stream);
+int zrc4_copy_states(zrc4_ctx *dst, const uint32_t *dst_ids, uint32_t dst_first,
+                     zrc4_ctx *src, const uint32_t *src_ids, uint32_t src_first,
+                     uint32_t n, void *stream);
+int zrc4_set_states(zrc4_ctx *ctx, uint32_t first_slot, uint32_t n,
+                    const uint8_t *sbox, const uint8_t *x, const uint8_t *y);
+
 const char *zrc4_strerror(int code);
 const char *zrc4_version(void);
 

@@ -178,6 +178,37 @@ class Context:
                                         int(max_packets), _ptr(npk), _ptr(used), _ptr(status), _ptr(pkt_len),
                                         _stream(stream)), "zrc4_frame_scan")
 
+    # -- state records: export / import / copy (device pointers) -----------
+    @staticmethod
+    def _count(n, ids, xy) -> int:
+        if n is not None:
+            return int(n)
+        return int((ids if ids is not None else xy).numel())
+
+    def export_states(self, sbox, xy, ids=None, first_slot: int = 0, n=None, stream=None) -> None:
+        """zrc4_export_states: record i = slot ids[i] (or first_slot + i) into
+        sbox (uint8[n, 256]) and xy (uint16[n], x | y << 8); n defaults to the
+        size of ids, else of xy."""
+        check(self._lib.zrc4_export_states(self._h, _ptr(ids), int(first_slot), self._count(n, ids, xy), _ptr(sbox),
+                                           _ptr(xy), _stream(stream)), "zrc4_export_states")
+
+    def import_states(self, sbox, xy, ids=None, first_slot: int = 0, n=None, stream=None) -> None:
+        """zrc4_import_states: the inverse of export_states."""
+        check(self._lib.zrc4_import_states(self._h, _ptr(ids), int(first_slot), self._count(n, ids, xy), _ptr(sbox),
+                                           _ptr(xy), _stream(stream)), "zrc4_import_states")
+
+    def copy_states(self, src_ctx: "Context", dst_ids=None, dst_first: int = 0, src_ids=None, src_first: int = 0,
+                    n=None, stream=None) -> None:
+        """zrc4_copy_states: slots of src_ctx (which may be this context) into
+        slots of this one, every source read before any destination is
+        written.  n defaults to the size of dst_ids, else of src_ids."""
+        if n is None:
+            if dst_ids is None and src_ids is None:
+                raise ValueError("copy_states: n is needed when neither side has ids")
+            n = (dst_ids if dst_ids is not None else src_ids).numel()
+        check(self._lib.zrc4_copy_states(self._h, _ptr(dst_ids), int(dst_first), src_ctx._h, _ptr(src_ids),
+                                         int(src_first), int(n), _stream(stream)), "zrc4_copy_states")
+
     def sync(self, stream=None) -> None:
         check(self._lib.zrc4_sync(self._h, _stream(stream)), "zrc4_sync")
 
@@ -241,6 +272,17 @@ class Context:
         check(self._lib.zrc4_get_states(self._h, int(first_slot), int(n), _ptr(sb), _ptr(x), _ptr(y)),
               "zrc4_get_states")
         return sb, x, y
+
+    def set_states(self, first_slot: int, sbox, x, y) -> None:
+        """zrc4_set_states: the inverse of get_states (host arrays; blocks)."""
+        sb = np.ascontiguousarray(sbox, dtype=np.uint8)
+        xv = np.ascontiguousarray(x, dtype=np.uint8)
+        yv = np.ascontiguousarray(y, dtype=np.uint8)
+        n = int(xv.size)
+        if sb.size != 256 * n or yv.size != n:
+            raise ValueError("set_states: sbox must be [n, 256] for n values of x and of y")
+        check(self._lib.zrc4_set_states(self._h, int(first_slot), n, _ptr(sb), _ptr(xv), _ptr(yv)),
+              "zrc4_set_states")
 
     def set_state(self, slot: int, sbox: bytes, x: int, y: int) -> None:
         if len(sbox) != 256:

@@ -62,6 +62,10 @@ SIGNATURES = [
     ("zrc4_get_state", C.c_int, [_P, C.c_uint32, _U8P, _U8P, _U8P]),
     ("zrc4_set_state", C.c_int, [_P, C.c_uint32, _U8P, C.c_uint8, C.c_uint8]),
     ("zrc4_get_states", C.c_int, [_P, C.c_uint32, C.c_uint32, _P, _P, _P]),
+    ("zrc4_export_states", C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, _P, _P]),
+    ("zrc4_import_states", C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, _P, _P]),
+    ("zrc4_copy_states", C.c_int, [_P, _P, C.c_uint32, _P, _P, C.c_uint32, C.c_uint32, _P]),
+    ("zrc4_set_states", C.c_int, [_P, C.c_uint32, C.c_uint32, _P, _P, _P]),
     ("zrc4_strerror", C.c_char_p, [C.c_int]),
     ("zrc4_version", C.c_char_p, []),
 ]

@@ -56,6 +56,15 @@ struct zrc4_ctx {
     hipEvent_t decl_ev[kDeclRing];
     bool decl_ev_live[kDeclRing];
     uint32_t decl_next;
+    // zrc4_copy_states' record scratch (n * 258 bytes: S-boxes, then x/y words),
+    // owned by the destination context; grown on demand and kept
+    uint8_t *copy_scratch;
+    size_t copy_scratch_bytes;
+    // the last copy's end: a copy on another stream waits for it before it
+    // reuses the scratch
+    hipEvent_t copy_ev;
+    hipStream_t copy_last;
+    bool copy_ev_live;
 };
 
 namespace {
@@ -290,6 +299,54 @@ int launch_ksa(zrc4_ctx *c, const uint32_t *ids, uint32_t first_slot, const uint
     return hipGetLastError() == hipSuccess ? ZRC4_OK : ZRC4_ERR_LAUNCH;
 }
 
+// Record export / import (zrc4_export_states and friends; kernels and paths:
+// zrc4_kernels.hpp).  Records move as 16-byte pieces, so sbox must be 16-byte
+// aligned.  gate / gate_cap: zrc4_copy_states' source ids, so that an entry
+// whose source was skipped is skipped on the import side too.
+bool records_ok(const void *sbox, const void *xy)
+{
+    return sbox && xy && ((uintptr_t)sbox & 15u) == 0u && ((uintptr_t)xy & 1u) == 0u;
+}
+
+uint32_t range_groups(uint32_t first_slot, uint32_t n)
+{
+    return ((first_slot + (n - 1u)) >> 8) - (first_slot >> 8) + 1u;
+}
+
+int launch_export(zrc4_ctx *c, const uint32_t *ids, uint32_t first_slot, uint32_t n, uint8_t *sbox, uint16_t *xy,
+                  hipStream_t s)
+{
+    if (n == 0) return ZRC4_OK;
+    if (!records_ok(sbox, xy)) return ZRC4_ERR_INVALID_ARG;
+    if (!ids) {
+        if ((uint64_t)first_slot + n > c->capacity) return ZRC4_ERR_SLOT_RANGE;
+        hipLaunchKernelGGL(zrc4::states_export_kernel<true>, dim3(range_groups(first_slot, n)), dim3(zrc4::kGroup), 0,
+                           s, c->arena, c->xy, ids, first_slot, n, c->capacity, sbox, xy, c->err);
+    } else {
+        const uint32_t buckets = (uint32_t)(((uint64_t)n + zrc4::kGroup - 1) / zrc4::kGroup);
+        hipLaunchKernelGGL(zrc4::states_export_kernel<false>, dim3(buckets), dim3(zrc4::kGroup), 0, s, c->arena,
+                           c->xy, ids, 0u, n, c->capacity, sbox, xy, c->err);
+    }
+    return hipGetLastError() == hipSuccess ? ZRC4_OK : ZRC4_ERR_LAUNCH;
+}
+
+int launch_import(zrc4_ctx *c, const uint32_t *ids, uint32_t first_slot, uint32_t n, const uint8_t *sbox,
+                  const uint16_t *xy, const uint32_t *gate, uint32_t gate_cap, hipStream_t s)
+{
+    if (n == 0) return ZRC4_OK;
+    if (!records_ok(sbox, xy)) return ZRC4_ERR_INVALID_ARG;
+    if (!ids) {
+        if ((uint64_t)first_slot + n > c->capacity) return ZRC4_ERR_SLOT_RANGE;
+        hipLaunchKernelGGL(zrc4::states_import_image_kernel, dim3(range_groups(first_slot, n)), dim3(zrc4::kGroup), 0,
+                           s, c->arena, c->xy, first_slot, n, sbox, xy, gate, gate_cap);
+    } else {
+        const uint32_t grid = (uint32_t)(((uint64_t)n + 3u) / 4u);
+        hipLaunchKernelGGL(zrc4::states_scatter_kernel, dim3(grid), dim3(256), 0, s, c->arena, c->xy, ids, n,
+                           c->capacity, sbox, xy, gate, gate_cap, c->err);
+    }
+    return hipGetLastError() == hipSuccess ? ZRC4_OK : ZRC4_ERR_LAUNCH;
+}
+
 // The per-iteration completion point of the session engine's hooks: ONE
 // stream wait, then the latch word is read straight from pinned memory (a
 // device-to-host copy of it used to cost another ~11 us per call).
@@ -375,6 +432,8 @@ int zrc4_destroy(zrc4_ctx *c)
     if (c->err) (void)hipHostFree(c->err);
     if (c->d_stage) (void)hipFree(c->d_stage);
     if (c->h_stage) (void)hipHostFree(c->h_stage);
+    if (c->copy_scratch) (void)hipFree(c->copy_scratch);
+    if (c->copy_ev) (void)hipEventDestroy(c->copy_ev);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
     return ZRC4_OK;
@@ -862,6 +921,91 @@ int zrc4_get_states(zrc4_ctx *c, uint32_t first_slot, uint32_t n, uint8_t *sbox,
         y[i] = (uint8_t)(v[i] >> 8);
     }
     return ZRC4_OK;
+}
+
+int zrc4_export_states(zrc4_ctx *c, const uint32_t *ids, uint32_t first_slot, uint32_t n, uint8_t *sbox,
+                       uint16_t *xy, void *stream)
+{
+    if (!c) return ZRC4_ERR_INVALID_ARG;
+    if (n == 0) return ZRC4_OK;
+    int rc = set_device(c);
+    if (rc) return rc;
+    return launch_export(c, ids, first_slot, n, sbox, xy, (hipStream_t)stream);
+}
+
+int zrc4_import_states(zrc4_ctx *c, const uint32_t *ids, uint32_t first_slot, uint32_t n, const uint8_t *sbox,
+                       const uint16_t *xy, void *stream)
+{
+    if (!c) return ZRC4_ERR_INVALID_ARG;
+    if (n == 0) return ZRC4_OK;
+    int rc = set_device(c);
+    if (rc) return rc;
+    return launch_import(c, ids, first_slot, n, sbox, xy, nullptr, 0u, (hipStream_t)stream);
+}
+
+int zrc4_copy_states(zrc4_ctx *dst, const uint32_t *dst_ids, uint32_t dst_first, zrc4_ctx *src,
+                     const uint32_t *src_ids, uint32_t src_first, uint32_t n, void *stream)
+{
+    if (!dst || !src || dst->device != src->device) return ZRC4_ERR_INVALID_ARG;
+    if (n == 0) return ZRC4_OK;
+    if (!dst_ids && (uint64_t)dst_first + n > dst->capacity) return ZRC4_ERR_SLOT_RANGE;
+    if (!src_ids && (uint64_t)src_first + n > src->capacity) return ZRC4_ERR_SLOT_RANGE;
+    int rc = set_device(dst);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    // One scratch for the whole call, never chunks: every source is exported
+    // before the first destination is written.
+    const size_t need = (size_t)n * ZRC4_STATE_BYTES;
+    if (need > dst->copy_scratch_bytes) {
+        ZRC4_TRY(hipStreamSynchronize(s));      // an earlier copy on this stream may still use the old scratch
+        size_t want = 1u << 20;
+        while (want < need) want <<= 1;
+        void *p = nullptr;
+        if (hipMalloc(&p, want) != hipSuccess) return ZRC4_ERR_OUT_OF_MEMORY;
+        if (dst->copy_scratch) (void)hipFree(dst->copy_scratch);
+        dst->copy_scratch = static_cast<uint8_t *>(p);
+        dst->copy_scratch_bytes = want;
+    }
+    if (dst->copy_ev_live && dst->copy_last != s) ZRC4_TRY(hipStreamWaitEvent(s, dst->copy_ev, 0));
+    uint8_t *sb = dst->copy_scratch;
+    uint16_t *xy = reinterpret_cast<uint16_t *>(sb + (size_t)n * 256u);
+    if ((rc = launch_export(src, src_ids, src_first, n, sb, xy, s))) return rc;
+    rc = launch_import(dst, dst_ids, dst_first, n, sb, xy, src_ids, src->capacity, s);
+    // mark where the scratch is free again; without an event, wait here
+    if (!dst->copy_ev && hipEventCreateWithFlags(&dst->copy_ev, hipEventDisableTiming) != hipSuccess)
+        dst->copy_ev = nullptr;
+    dst->copy_ev_live = dst->copy_ev && hipEventRecord(dst->copy_ev, s) == hipSuccess;
+    dst->copy_last = s;
+    if (!dst->copy_ev_live) (void)hipStreamSynchronize(s);
+    return rc;
+}
+
+int zrc4_set_states(zrc4_ctx *c, uint32_t first_slot, uint32_t n, const uint8_t *sbox, const uint8_t *x,
+                    const uint8_t *y)
+{
+    if (!c) return ZRC4_ERR_INVALID_ARG;
+    if (n == 0) return ZRC4_OK;
+    if (!sbox || !x || !y) return ZRC4_ERR_INVALID_ARG;
+    if ((uint64_t)first_slot + n > c->capacity) return ZRC4_ERR_SLOT_RANGE;
+    int rc = set_device(c);
+    if (rc) return rc;
+    const size_t o_xy = (size_t)n * 256u, total = align16(o_xy + (size_t)n * 2u);
+    if ((rc = grow_stage(c, total))) return rc;
+    par_memcpy(c->h_stage, sbox, o_xy);
+    uint16_t *v = reinterpret_cast<uint16_t *>(c->h_stage + o_xy);
+    for (uint32_t i = 0; i < n; ++i) v[i] = (uint16_t)(x[i] | (y[i] << 8));
+    uint8_t *st = c->h_stage;
+    if (total > kZeroCopyMax) {
+        ZRC4_TRY(hipMemcpyAsync(c->d_stage, c->h_stage, total, hipMemcpyHostToDevice, c->stream));
+        st = c->d_stage;
+    }
+    rc = launch_import(c, nullptr, first_slot, n, st, reinterpret_cast<const uint16_t *>(st + o_xy), nullptr, 0u,
+                       c->stream);
+    if (rc) {
+        (void)hipStreamSynchronize(c->stream);     // a queued H2D still reads the staging buffer
+        return rc;
+    }
+    return check_err(c, c->stream);
 }
 
 const char *zrc4_strerror(int code)

@@ -3264,4 +3264,325 @@ identity_kernel(uint8_t *__restrict__ arena)
     }
 }
 
+// ---------------------------------------------------------------------------
+// Bulk state export / import (zrc4_export_states, zrc4_import_states,
+// zrc4_copy_states, zrc4_set_states).
+//
+// A record is a slot's 256 S-box bytes in index order; the arena keeps them
+// as one column of its group's image (byte k of slot j at (k << 8) |
+// col_of(j)), so moving records is a 256 x 256 byte transposition plus the
+// column permutation.
+//
+// Image path (states_export_kernel on one-group buckets and on ranges,
+// states_import_image_kernel on ranges): one 256-thread workgroup per group.
+// The image moves between HBM and LDS as coalesced 16-byte pieces per lane;
+// records move as 16-byte pieces per lane, 8 lanes to a 128-byte line.  In
+// between a lane owns "units" of 16 rows x 4 columns (16 LDS dwords): a unit
+// is four 4x4 byte transposes (v_perm_b32) away from the four 16-byte record
+// pieces S[16a .. 16a+15] of its columns.  LDS layout: row r (256 bytes)
+// rotated left by ((r >> 4) & 7) 16-byte pieces,
+//     dword(r, c) at (r << 6) | ((c + 4 ((r >> 4) & 7)) & 63),
+// so that the 32 lanes of a ds_read_b32 / ds_write_b32 group (a & 7 = 0..7,
+// four neighbouring c) fall on banks c + 4 (a & 7): 32 distinct ones (an
+// unrotated image would put the 8 rows 16 a + t of one dword column on one
+// bank).  The rotation is whole 16-byte pieces, so the image side stays
+// ds_write_b128 / ds_read_b128, 8 contiguous lanes on 8 distinct pieces of
+// one row.  65 KiB of LDS with the tables: two workgroups per CU.
+//
+// Gather / scatter path (export buckets that mix groups, name a slot twice or
+// have at most ZRC4_STATES_GATHER_MAX busy entries; every import by ids): one
+// wave per entry, lane l moves S[4l .. 4l+3] as four byte accesses at the
+// image's 256-byte stride and one dword of the record (a coalesced 256-byte
+// access per wave).  Import by ids stores BYTES into the image: another wave
+// of the same launch may own the neighbouring columns.
+//
+// Every id is compared with the capacity before any address is formed from
+// it; ZRC4_IDLE_SLOT entries are skipped silently, other ids >= capacity
+// latch kErrSlotRange and are skipped.
+// ---------------------------------------------------------------------------
+#ifndef ZRC4_STATES_GATHER_MAX
+#define ZRC4_STATES_GATHER_MAX 4   // export buckets with at most this many busy entries gather
+#endif
+constexpr uint32_t kNoRec = 0xFFFFFFFFu;
+constexpr uint32_t kIdle = 0xFFFFFFFFu;   // ZRC4_IDLE_SLOT
+
+__host__ __device__ __forceinline__ uint32_t byte_perm(uint32_t hi, uint32_t lo, uint32_t sel)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_perm(hi, lo, sel);
+#else
+    const uint64_t v = ((uint64_t)hi << 32) | lo;
+    uint32_t r = 0;
+    for (int b = 0; b < 4; ++b) r |= (uint32_t)((v >> (8u * ((sel >> (8 * b)) & 7u))) & 255u) << (8 * b);
+    return r;
+#endif
+}
+
+// 4x4 byte transpose: byte i of d[t] <-> byte t of d[i].
+__host__ __device__ __forceinline__ void transpose4x4(uint32_t &d0, uint32_t &d1, uint32_t &d2, uint32_t &d3)
+{
+    const uint32_t lo01 = byte_perm(d1, d0, 0x05010400u), hi01 = byte_perm(d1, d0, 0x07030602u);
+    const uint32_t lo23 = byte_perm(d3, d2, 0x05010400u), hi23 = byte_perm(d3, d2, 0x07030602u);
+    d0 = byte_perm(lo23, lo01, 0x05040100u);
+    d1 = byte_perm(lo23, lo01, 0x07060302u);
+    d2 = byte_perm(hi23, hi01, 0x05040100u);
+    d3 = byte_perm(hi23, hi01, 0x07060302u);
+}
+
+__host__ __device__ __forceinline__ uint32_t st_dw(uint32_t r, uint32_t c)   // LDS dword of image dword (r, c)
+{
+    return (r << 6) | ((c + (((r >> 4) & 7u) << 2)) & 63u);
+}
+__host__ __device__ __forceinline__ uint32_t st_q(uint32_t r, uint32_t p)    // LDS 16-byte piece of image piece (r, p)
+{
+    return (r << 4) | ((p + ((r >> 4) & 7u)) & 15u);
+}
+// Unit `pass` (0..3) of thread tid: rows 16 a .. 16 a + 15 of dword column c.
+__host__ __device__ __forceinline__ void st_unit(uint32_t tid, uint32_t pass, uint32_t &a, uint32_t &c)
+{
+    const uint32_t l = tid & 63u, w = tid >> 6;
+    a = (l & 7u) | ((pass & 1u) << 3);
+    c = (l >> 3) | ((2u * w + (pass >> 1)) << 3);
+}
+
+__host__ __device__ __forceinline__ void st_image_to_lds(u32x4 *L, const uint8_t *img, uint32_t tid)
+{
+    const u32x4 *src = reinterpret_cast<const u32x4 *>(img);
+    u32x4 v[16];
+#pragma unroll
+    for (uint32_t i = 0; i < 16; ++i) v[i] = src[i * 256u + tid];
+#pragma unroll
+    for (uint32_t i = 0; i < 16; ++i) {
+        const uint32_t q = i * 256u + tid;
+        L[st_q(q >> 4, q & 15u)] = v[i];
+    }
+}
+
+__host__ __device__ __forceinline__ void st_lds_to_image(uint8_t *img, const u32x4 *L, uint32_t tid)
+{
+    u32x4 *dst = reinterpret_cast<u32x4 *>(img);
+#pragma unroll
+    for (uint32_t i = 0; i < 16; ++i) {
+        const uint32_t q = i * 256u + tid;
+        dst[q] = L[st_q(q >> 4, q & 15u)];
+    }
+}
+
+// LDS image -> the records rec[col] of the thread's units (kNoRec: none).
+__host__ __device__ __forceinline__ void st_export_units(const u32x4 *L, const uint32_t *rec, uint8_t *sbox,
+                                                         uint32_t tid)
+{
+    const uint32_t *Ld = reinterpret_cast<const uint32_t *>(L);
+#pragma unroll 1
+    for (uint32_t pass = 0; pass < 4; ++pass) {
+        uint32_t a, c;
+        st_unit(tid, pass, a, c);
+        const u32x4 rc = reinterpret_cast<const u32x4 *>(rec)[c];
+        uint32_t d[16];
+#pragma unroll
+        for (uint32_t t = 0; t < 16; ++t) d[t] = Ld[st_dw(16u * a + t, c)];
+#pragma unroll
+        for (uint32_t m = 0; m < 4; ++m) transpose4x4(d[4 * m], d[4 * m + 1], d[4 * m + 2], d[4 * m + 3]);
+#pragma unroll
+        for (uint32_t i = 0; i < 4; ++i)
+            if (rc[i] != kNoRec) {
+                u32x4 piece;
+                piece[0] = d[i];
+                piece[1] = d[4 + i];
+                piece[2] = d[8 + i];
+                piece[3] = d[12 + i];
+                *reinterpret_cast<u32x4 *>(sbox + (size_t)rc[i] * 256u + 16u * a) = piece;
+            }
+    }
+}
+
+// The records rec[col] of the thread's units -> LDS image; columns without a
+// record keep their bytes.
+__host__ __device__ __forceinline__ void st_import_units(u32x4 *L, const uint32_t *rec, const uint8_t *sbox,
+                                                         uint32_t tid)
+{
+    uint32_t *Ld = reinterpret_cast<uint32_t *>(L);
+#pragma unroll 1
+    for (uint32_t pass = 0; pass < 4; ++pass) {
+        uint32_t a, c;
+        st_unit(tid, pass, a, c);
+        const u32x4 rc = reinterpret_cast<const u32x4 *>(rec)[c];
+        uint32_t d[16], mask = 0;
+#pragma unroll
+        for (uint32_t i = 0; i < 4; ++i) {
+            u32x4 piece = {0u, 0u, 0u, 0u};
+            if (rc[i] != kNoRec) {
+                piece = *reinterpret_cast<const u32x4 *>(sbox + (size_t)rc[i] * 256u + 16u * a);
+                mask |= 0xFFu << (8u * i);
+            }
+            d[i] = piece[0];
+            d[4 + i] = piece[1];
+            d[8 + i] = piece[2];
+            d[12 + i] = piece[3];
+        }
+        if (mask == 0u) continue;
+#pragma unroll
+        for (uint32_t m = 0; m < 4; ++m) transpose4x4(d[4 * m], d[4 * m + 1], d[4 * m + 2], d[4 * m + 3]);
+        if (mask == 0xFFFFFFFFu) {
+#pragma unroll
+            for (uint32_t t = 0; t < 16; ++t) Ld[st_dw(16u * a + t, c)] = d[t];
+        } else {
+#pragma unroll
+            for (uint32_t t = 0; t < 16; ++t) {
+                uint32_t &o = Ld[st_dw(16u * a + t, c)];
+                o = (o & ~mask) | (d[t] & mask);
+            }
+        }
+    }
+}
+
+// One wave, one entry: lane l moves S[4l .. 4l+3] between the slot's image
+// column and dword l of the record.
+__device__ __forceinline__ void st_gather_record(const uint8_t *arena, uint32_t slot, uint8_t *rec, uint32_t l)
+{
+    const uint8_t *p = arena + (size_t)(slot >> 8) * kGroupBytes + col_of(slot & 255u) + ((size_t)l << 10);
+    const uint32_t v = (uint32_t)p[0] | ((uint32_t)p[256] << 8) | ((uint32_t)p[512] << 16) | ((uint32_t)p[768] << 24);
+    reinterpret_cast<uint32_t *>(rec)[l] = v;
+}
+
+__device__ __forceinline__ void st_scatter_record(uint8_t *arena, uint32_t slot, const uint8_t *rec, uint32_t l)
+{
+    uint8_t *p = arena + (size_t)(slot >> 8) * kGroupBytes + col_of(slot & 255u) + ((size_t)l << 10);
+    const uint32_t v = reinterpret_cast<const uint32_t *>(rec)[l];
+    p[0] = (uint8_t)v;
+    p[256] = (uint8_t)(v >> 8);
+    p[512] = (uint8_t)(v >> 16);
+    p[768] = (uint8_t)(v >> 24);
+}
+
+// states_export_kernel: workgroup b exports entries [256 b, 256 b + 256)
+// (RANGE: the slots of group (first_slot >> 8) + b that lie in [first_slot,
+// first_slot + n), entry = slot - first_slot) to sbox[256 e ..] and xy[e].
+template <bool RANGE>
+__global__ void __launch_bounds__(256, 2)
+states_export_kernel(const uint8_t *__restrict__ arena, const uint16_t *__restrict__ xy,
+                     const uint32_t *__restrict__ ids, uint32_t first_slot, uint32_t n, uint32_t capacity,
+                     uint8_t *__restrict__ sbox, uint16_t *__restrict__ out_xy, uint32_t *err)
+{
+    __shared__ u32x4 L[kGroupBytes / 16];
+    __shared__ __attribute__((aligned(16))) uint32_t rec[256];
+    __shared__ uint32_t lst[256];          // ids buckets: the busy entries, compacted
+    __shared__ uint32_t sid[256];
+    __shared__ uint32_t vote[4];           // group min, group max, busy entries, a slot named twice
+    const uint32_t tid = threadIdx.x;
+    uint32_t id = kIdle, e = 0, g = 0;
+    bool ok = false;
+    if (RANGE) {
+        g = (first_slot >> 8) + blockIdx.x;
+        id = (g << 8) | tid;
+        ok = id >= first_slot && id - first_slot < n;
+        e = id - first_slot;
+        rec[col_of(tid)] = ok ? e : kNoRec;
+        __syncthreads();
+    } else {
+        const uint64_t e64 = (uint64_t)blockIdx.x * 256u + tid;
+        e = (uint32_t)e64;
+        if (e64 < n) id = ids[e64];
+        ok = id != kIdle;
+        if (ok && id >= capacity) {
+            latch_fault(err, kErrSlotRange);
+            ok = false;
+        }
+        if (tid == 0) {
+            vote[0] = 0xFFFFFFFFu;
+            vote[1] = 0u;
+            vote[2] = 0u;
+            vote[3] = 0u;
+        }
+        rec[tid] = kNoRec;
+        sid[tid] = ok ? id : kIdle;
+        __syncthreads();
+        if (ok) {
+            atomicMin(&vote[0], id >> 8);
+            atomicMax(&vote[1], id >> 8);
+            lst[atomicAdd(&vote[2], 1u)] = tid;
+        }
+        __syncthreads();
+        const uint32_t busy = vote[2];
+        if (busy == 0u) return;
+        bool image = vote[0] == vote[1] && busy > (uint32_t)ZRC4_STATES_GATHER_MAX;
+        if (image) {
+            const uint32_t col = col_of(id & 255u);
+            if (ok) rec[col] = e;
+            __syncthreads();
+            if (ok && rec[col] != e) vote[3] = 1u;     // the slot has a second entry: each needs its record
+            __syncthreads();
+            image = vote[3] == 0u;
+        }
+        if (!image) {
+            const uint32_t w = tid >> 6, l = tid & 63u;
+            for (uint32_t k = w; k < busy; k += 4u) {
+                const uint32_t t = lst[k], slot = sid[t];
+                const uint64_t ek = (uint64_t)blockIdx.x * 256u + t;
+                st_gather_record(arena, slot, sbox + ek * 256u, l);
+                if (l == 0u) out_xy[ek] = xy[slot];
+            }
+            return;
+        }
+        g = vote[0];
+    }
+    if (ok) out_xy[e] = xy[id];
+    st_image_to_lds(L, arena + (size_t)g * kGroupBytes, tid);
+    __syncthreads();
+    st_export_units(L, rec, sbox, tid);
+}
+
+// states_import_image_kernel: workgroup b imports the slots of group
+// (first_slot >> 8) + b that lie in [first_slot, first_slot + n) from records
+// slot - first_slot.  A partly covered group is read, merged and written back
+// whole (a range call gives each group to exactly one workgroup).  gate (the
+// source ids of zrc4_copy_states, or NULL): entry e is skipped when gate[e]
+// is not a slot below gate_cap, whose record was therefore never exported.
+__global__ void __launch_bounds__(256, 2)
+states_import_image_kernel(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy, uint32_t first_slot, uint32_t n,
+                           const uint8_t *__restrict__ sbox, const uint16_t *__restrict__ in_xy,
+                           const uint32_t *__restrict__ gate, uint32_t gate_cap)
+{
+    __shared__ u32x4 L[kGroupBytes / 16];
+    __shared__ __attribute__((aligned(16))) uint32_t rec[256];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t g = (first_slot >> 8) + blockIdx.x, id = (g << 8) | tid;
+    bool ok = id >= first_slot && id - first_slot < n;
+    const uint32_t e = id - first_slot;
+    if (ok && gate) ok = gate[e] < gate_cap;
+    rec[col_of(tid)] = ok ? e : kNoRec;
+    const int cnt = __syncthreads_count(ok);
+    if (cnt == 0) return;
+    uint8_t *img = arena + (size_t)g * kGroupBytes;
+    if (cnt != 256) {
+        st_image_to_lds(L, img, tid);
+        __syncthreads();
+    }
+    if (ok) xy[id] = in_xy[e];
+    st_import_units(L, rec, sbox, tid);
+    __syncthreads();
+    st_lds_to_image(img, L, tid);
+}
+
+// states_scatter_kernel: import by ids, one wave per entry (4 per workgroup).
+__global__ void __launch_bounds__(256)
+states_scatter_kernel(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy, const uint32_t *__restrict__ ids,
+                      uint32_t n, uint32_t capacity, const uint8_t *__restrict__ sbox,
+                      const uint16_t *__restrict__ in_xy, const uint32_t *__restrict__ gate, uint32_t gate_cap,
+                      uint32_t *err)
+{
+    const uint32_t l = threadIdx.x & 63u;
+    const uint64_t e = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (e >= n) return;
+    const uint32_t id = ids[e];
+    if (id == kIdle) return;
+    if (id >= capacity) {
+        if (l == 0u) latch_fault(err, kErrSlotRange);
+        return;
+    }
+    if (gate && gate[e] >= gate_cap) return;
+    st_scatter_record(arena, id, sbox + e * 256u, l);
+    if (l == 0u) xy[id] = in_xy[e];
+}
+
 }  // namespace zrc4

@@ -454,11 +454,17 @@ int zrc4_ks_copy(zrc4_ks *dk, uint32_t dst, zrc4_ks *sk, uint32_t src)
     if (S.lost) return ZRC4_ERR_STATE;
     const uint64_t buffered = S.gen - S.use;
     if (buffered > dk->ring) return ZRC4_ERR_INVALID_ARG;
-    uint8_t sb[256], x = 0, y = 0;
-    if ((rc = set_device(sk->c)) != ZRC4_OK) return rc;
-    if ((rc = zrc4_get_state(sk->c, src, sb, &x, &y)) != ZRC4_OK) return rc;   // the state at S.gen
-    if ((rc = set_device(dk->c)) != ZRC4_OK) return rc;
-    if ((rc = zrc4_set_state(dk->c, dst, sb, x, y)) != ZRC4_OK) return rc;
+    if (dk->c->device == sk->c->device) {
+        // the state at S.gen, slot to slot on the device: two launches, one wait
+        if ((rc = zrc4_copy_states(dk->c, nullptr, dst, sk->c, nullptr, src, 1, dk->c->stream)) != ZRC4_OK) return rc;
+        if ((rc = check_err(dk->c, dk->c->stream)) != ZRC4_OK) return rc;
+    } else {
+        uint8_t sb[256], x = 0, y = 0;
+        if ((rc = set_device(sk->c)) != ZRC4_OK) return rc;
+        if ((rc = zrc4_get_state(sk->c, src, sb, &x, &y)) != ZRC4_OK) return rc;   // the state at S.gen
+        if ((rc = set_device(dk->c)) != ZRC4_OK) return rc;
+        if ((rc = zrc4_set_state(dk->c, dst, sb, x, y)) != ZRC4_OK) return rc;
+    }
     dk->resetRing(dst);
     if (buffered) {
         uint8_t *sr = sk->ringOf(src), *dr = dk->ringOf(dst);
