@@ -497,6 +497,7 @@ def test_window_path_ragged(built, torch_cuda, first_slot, n):
     (100, 20 * 256),                           # few groups but unaligned: no window kernel
     (0, 200 * 256 - 7),                        # whole-group kernel: 3 XCD-run blocks of 64 + a tail of 8
     (37, 150 * 256),                           # unaligned range over 151 groups (gathered columns, runs + tail)
+    (37, (256 + 4) * 256),                     # unaligned range above CUs groups: persistent kernel, ids == NULL
 ])
 def test_dispatch_boundaries_bit_exact(built, torch_cuda, first_slot, n):
     """zrc4.hip launch_crypt picks the kernel from the batch's group count
