@@ -368,7 +368,7 @@ int zrc4_set_states(zrc4_ctx *ctx, uint32_t first_slot, uint32_t n,
                     const uint8_t *sbox, const uint8_t *x, const uint8_t *y);
 
 const char *zrc4_strerror(int code);
-const char *zrc4_version(void);
+const char *zrc4_version(void);   /* a non-product build appends " [KNOB=value]" per build knob set */
 
 #ifdef __cplusplus
 }

@@ -58,6 +58,45 @@ def test_strerror_and_version(built):
     assert b"gfx950" in lib.zrc4_version()
 
 
+def test_product_version_is_plain(built):
+    """The shipped library names no build knob: it is the product."""
+    from zsummerx_amd import _capi, build
+    assert _capi.load(build.LIB).zrc4_version() == b"zrc4-mi355x 0.2 (gfx950)"
+
+
+def test_variant_version_names_its_knobs(built):
+    """A library built with a knob set says so (no device is touched)."""
+    from zsummerx_amd import _capi, build
+    for name, defs in build.TEST_VARIANTS.items():
+        version = _capi.load(build.PKG / f"libzrc4_{name}.so").zrc4_version().decode()
+        assert version.startswith("zrc4-mi355x 0.2 (gfx950) ["), (name, version)
+        for k, v in defs.items():
+            assert f"{k}={v}" in version, (name, version)
+
+
+def test_test_variants_use_kept_knobs_only():
+    from zsummerx_amd import build
+    for defs in build.TEST_VARIANTS.values():
+        assert set(defs) <= set(build.KEPT_KNOBS)
+
+
+@pytest.mark.parametrize("knob", ["ZRC4_AB_LDS", "ZRC4_BLK_DEFER"])
+def test_removed_knob_is_refused_before_any_build(knob, monkeypatch):
+    """A knob the sources no longer read would build a copy of the product
+    under a variant's name: refused, with the way to the revision that had it."""
+    from zsummerx_amd import build
+
+    def no_compiler(*a, **k):
+        raise AssertionError("a process was started for a refused build")
+    monkeypatch.setattr(build.subprocess, "run", no_compiler)
+    out = build.PKG / "libzrc4_x.so"
+    assert not out.exists()
+    with pytest.raises(ValueError) as ei:
+        build.build_variant("x", {knob: 1})
+    assert knob in str(ei.value) and f"x@<rev>:{knob}=1" in str(ei.value)
+    assert not out.exists()
+
+
 def test_no_device_is_a_loud_error(built):
     import torch
     if torch.cuda.device_count() > 0:

@@ -9,8 +9,14 @@ outputs of one batch are compared byte-for-byte across variants (they must be
 identical); then timed rounds are interleaved and the median per-launch time
 (HIP events on the launch stream) is reported per variant.
 
-  python tools/ab_bench.py --variant base: --variant o1:ZRC4_STEP_ORDER=1 \
-      --workloads cfg2,cfg3,cfg5 --rounds 7 --launches 20
+  python tools/ab_bench.py --variant base: --variant pc1:ZRC4_GR_PRECLAIM_MAX=1 \
+      --workloads cfg2,cfg3,cfg5 --rounds 7 --launches 20 --ids grouped
+
+Without a revision only the knobs in zsummerx_amd.build.KEPT_KNOBS build.  A
+removed ablation is built from the sources of the revision that still had it
+(DESIGN.md 3.6), timing-only ones with --no-check:
+
+  python tools/ab_bench.py --variant base: --variant noimg0@<rev>:ZRC4_AB_NOIMG0=1 --no-check
 """
 from __future__ import annotations
 

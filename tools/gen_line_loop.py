@@ -40,7 +40,6 @@ from pathlib import Path
 
 ROOT = Path(__file__).resolve().parents[1]
 OUT = ROOT / "zsummerx_amd" / "csrc" / "zrc4_line_loop.inc"
-OUT_AB = ROOT / "zsummerx_amd" / "csrc" / "ab" / "zrc4_line_loop_ab.inc"
 
 P_BASE, Q_BASE, X_BASE = 40, 72, 104      # 8 + 8 + 4 tuples of 4 VGPRs
 ADDR_BASE = 120                            # 8 x 64-bit store addresses (chunk i of session 8g+q)
@@ -125,14 +124,13 @@ def zl_block(base: int) -> str:
 
 
 def half(name: str, cur: int, ab: int = 0, last: bool = False) -> str:
-    """ab (timing-only A/B builds, zrc4_line_loop_ab.inc; outputs are wrong):
-    1 stores to the lane's sink slot (one 64 KiB sink for the whole chip:
-    contended), 2 loads from it, 3 no transpose, 4 both sinks.  (r02's 5 / 6,
-    a sink load in place of each store, were removed in r03: those loads
-    landed in the store-address temporaries v144-v151 asynchronously, and
-    crypt_last_half_next_asm ends on vmcnt(8), so they could still be in
-    flight when the compiler reused those registers -- a cfg5 A/B run with
-    them faulted the GPU.)"""
+    """ab: 0 the product's loop; 5 the --hazard-demo text (write_hazard_demo).
+    5 is r02's timing ablation with a sink load in place of each store, removed
+    in r03: those loads landed in the store-address temporaries v144-v151
+    asynchronously, and crypt_last_half_next_asm ends on vmcnt(8), so they
+    could still be in flight when the compiler reused those registers -- a
+    cfg5 A/B run with them faulted the GPU.  (The other timing ablations, 1-4:
+    sink stores, sink loads, no transpose, both sinks, are in the history.)"""
     start = {c: cur + 4 * c for c in range(8)}
     tl, final, ops, _ = transpose_plan(start, [X_BASE + 4 * t for t in range(4)])
     simulate(ops, start, final)
@@ -179,11 +177,8 @@ def half(name: str, cur: int, ab: int = 0, last: bool = False) -> str:
     w(q("s_mov_b64 exec, %[full]"))
     w(q("s_nop 4"))                                    # exec write -> DPP
     # 3. transpose
-    if ab != 3:
-        for line in tl:
-            w(q(line))
-    else:
-        final = dict(start)
+    for line in tl:
+        w(q(line))
     # 4. stores: chunk i of session 8g+q's line, or the sink past its last block
     for qq in range(8):
         sa = SA0 if qq % 2 == 0 else SA1
@@ -191,8 +186,6 @@ def half(name: str, cur: int, ab: int = 0, last: bool = False) -> str:
         w(q(f"v_cmp_gt_u32_e64 %[msk], v{LIM_BASE + qq}, %[sb]"))
         w(q(f"v_cndmask_b32_e64 v{sa}, v{SINK}, v{a}, %[msk]"))
         w(q(f"v_cndmask_b32_e64 v{sa + 1}, v{SINK + 1}, v{a + 1}, %[msk]"))
-        if ab in (1, 4):
-            sa = SINK
         if ab == 5:
             # the round-2 "sink load in place of each store" ablation that
             # faulted the GPU in round 3: the load lands in the store-address
@@ -215,16 +208,14 @@ def half(name: str, cur: int, ab: int = 0, last: bool = False) -> str:
     w(q("v_cmp_lt_u32_e64 %[msk], %[s1], %[nblk]"))
     w(q(f"v_cndmask_b32_e64 v{LA}, v{SINK}, %[palo], %[msk]"))
     w(q(f"v_cndmask_b32_e64 v{LA + 1}, v{SINK + 1}, %[pahi], %[msk]"))
-    la = SINK if ab in (2, 4) else LA
-    lb = SINK if ab in (2, 4) else LB
     for d in range(4):
-        w(f'"global_load_dwordx4 v[{cur + 4 * d}:{cur + 4 * d + 3}], v[{la}:{la + 1}], off offset:{16 * d}\\n\\t"')
+        w(f'"global_load_dwordx4 v[{cur + 4 * d}:{cur + 4 * d + 3}], v[{LA}:{LA + 1}], off offset:{16 * d}\\n\\t"')
     w(q("s_add_u32 %[s1], %[sb], 5"))
     w(q("v_cmp_lt_u32_e64 %[msk], %[s1], %[nblk]"))
     w(q(f"v_cndmask_b32_e64 v{LB}, v{SINK}, %[palo], %[msk]"))
     w(q(f"v_cndmask_b32_e64 v{LB + 1}, v{SINK + 1}, %[pahi], %[msk]"))
     for d in range(4):
-        w(f'"global_load_dwordx4 v[{cur + 16 + 4 * d}:{cur + 16 + 4 * d + 3}], v[{lb}:{lb + 1}], off offset:{64 + 16 * d}\\n\\t"')
+        w(f'"global_load_dwordx4 v[{cur + 16 + 4 * d}:{cur + 16 + 4 * d + 3}], v[{LB}:{LB + 1}], off offset:{64 + 16 * d}\\n\\t"')
     w(q("v_add_co_u32_e32 %[palo], vcc, 0x80, %[palo]"))
     w(q("v_addc_co_u32_e32 %[pahi], vcc, 0, %[pahi], vcc"))
     w(q(f"LL_{name}L_%=:"))
@@ -244,10 +235,7 @@ def transpose_only(name: str, cur: int) -> str:
             f"#define ZRC4_LL_FINAL_{name} {fin}\n")
 
 
-def main(ab_only: bool = False):
-    if ab_only:
-        write_ab()
-        return
+def main():
     text = [
         "// GENERATED by tools/gen_line_loop.py -- do not edit by hand.\n",
         "// Throughput-regime message loop of crypt_kernel (zrc4_kernels.hpp,\n",
@@ -279,22 +267,8 @@ def write_hazard_demo(out_dir: Path) -> Path:
     return out
 
 
-def write_ab():
-    """The timing-only variants are generated on demand (build_variant runs
-    this for ZRC4_LL_AB builds) and kept out of the tree."""
-    ab = ["// GENERATED by tools/gen_line_loop.py -- do not edit by hand.\n",
-          "// Timing-only A/B variants of zrc4_line_loop.inc (outputs are WRONG), selected by\n",
-          "// ZRC4_LL_AB: 1 stores to the sink, 2 loads from the sink, 3 no transpose, 4 both sinks.\n",
-          "#pragma once\n"]
-    for v in (1, 2, 3, 4):
-        ab += [f"#if ZRC4_LL_AB == {v}\n", half("P", P_BASE, v), half("Q", Q_BASE, v), "#endif\n"]
-    OUT_AB.parent.mkdir(exist_ok=True)
-    OUT_AB.write_text("".join(ab))
-    print("wrote", OUT_AB)
-
-
 if __name__ == "__main__":
     if "--hazard-demo" in sys.argv[1:]:
         print("wrote", write_hazard_demo(Path(sys.argv[sys.argv.index("--hazard-demo") + 1])))
     else:
-        main(ab_only="--ab" in sys.argv[1:])
+        main()

@@ -13,7 +13,6 @@ from __future__ import annotations
 import os
 import shutil
 import subprocess
-import sys
 from pathlib import Path
 
 PKG = Path(__file__).resolve().parent
@@ -62,16 +61,24 @@ def build_lib(force: bool = False, extra_flags=()) -> Path:
     return LIB
 
 
+# The -D switches the sources still read; every one of them
+# computes what the product computes, and zrc4_version() names those set.
+KEPT_KNOBS = ("ZRC4_TIMING", "ZRC4_WIN_TAG_LIMIT", "ZRC4_TEST_HOOKS", "ZRC4_GR_PRECLAIM_MAX",
+              "ZRC4_STATES_GATHER_MAX")
+
+
 def build_variant(name: str, defines: dict, rev: str | None = None) -> Path:
-    """A/B builds: the same library under another name with -D switches, or
-    the sources of git revision `rev` (tools/ab_bench.py loads several side by
-    side in one process)."""
+    """A/B builds: the same library under another name with -D switches (of
+    this tree: KEPT_KNOBS only), or the sources of git revision `rev` with any
+    switches that revision had (tools/ab_bench.py loads several side by side
+    in one process)."""
+    if not rev:
+        for k in defines:
+            if k.startswith("ZRC4_") and k not in KEPT_KNOBS:
+                raise ValueError(f"{k} is not a build knob of this tree (kept: {', '.join(KEPT_KNOBS)}); removed "
+                                 f"ablations are built from history with {name}@<rev>:{k}=1")
     out = PKG / f"libzrc4_{name}.so"
     srcs, inc, deps = HIP_SOURCES, ROOT / "include", HIP_DEPS
-    ab_inc = PKG / "csrc" / "ab" / "zrc4_line_loop_ab.inc"
-    if defines.get("ZRC4_LL_AB") and not rev and not ab_inc.exists():
-        # timing-only variants, generated on demand (tools/gen_line_loop.py --ab)
-        subprocess.run([sys.executable, str(ROOT / "tools" / "gen_line_loop.py"), "--ab"], check=True)
     if rev and not (ROOT / ".git").exists():      # the GPU box: no history, use the prebuilt library
         if not out.exists():
             raise FileNotFoundError(f"{out} (revision {rev}) must be built before the GPU run")

@@ -16,15 +16,6 @@
 #include <new>
 #include <thread>
 
-#ifndef ZRC4_HALF
-#define ZRC4_HALF 1   // A/B knob: 0 runs few-group range batches on whole-group workgroups too
-#endif
-#ifndef ZRC4_WIN_MAX_GROUPS
-#define ZRC4_WIN_MAX_GROUPS 32   // aligned range and grouped batches of at most this many groups run
-                                 // 16 lanes per stream (crypt_win_kernel, zrc4_win.hpp); 0 = never
-#endif
-static_assert(ZRC4_WIN_MAX_GROUPS <= zrc4::kWinMaxBuckets, "declared window groups travel in WinGroups");
-
 struct zrc4_ctx {
     int device;
     int num_cus;
@@ -142,9 +133,10 @@ int launch_crypt(zrc4_ctx *c, int mode, const uint32_t *ids, uint32_t first_slot
     // (the grouped stream kernel computes entry indexes of the bucket after
     // next in 32 bits)
     if (mode == zrc4::kGrouped && stream_kernel && n > 0xFFF00000u) return ZRC4_ERR_INVALID_ARG;
-    // Few aligned groups: 16 lanes per stream (speculative windows), one wave
-    // per 4 streams, 64 workgroups per group.
-    if (grid <= (uint32_t)ZRC4_WIN_MAX_GROUPS &&
+    // Few aligned groups (at most kWinMaxBuckets, so that declared groups
+    // travel in WinGroups): 16 lanes per stream (speculative windows,
+    // crypt_win_kernel), one wave per 4 streams, 64 workgroups per group.
+    if (grid <= zrc4::kWinMaxBuckets &&
         ((mode == zrc4::kRange && (first_slot & 255u) == 0u) || mode == zrc4::kGrouped)) {
         const dim3 wgrid(64u * grid), wblk(64);
         const zrc4::FrameArgs fa = fr ? *fr : zrc4::FrameArgs{};
@@ -175,7 +167,7 @@ int launch_crypt(zrc4_ctx *c, int mode, const uint32_t *ids, uint32_t first_slot
         zrc4::BucketGroups dg{};
         for (uint32_t b = 0; b < grid; ++b) dg.g[b] = decl[b];
         const zrc4::FrameArgs fa = fr ? *fr : zrc4::FrameArgs{};
-        const bool half = ZRC4_HALF && 2u * grid <= (uint32_t)c->num_cus;
+        const bool half = 2u * grid <= (uint32_t)c->num_cus;
 #define ZRC4_DECL(FRAME_, HALF_, GRID_, BLK_)                                                                  \
     hipLaunchKernelGGL((zrc4::crypt_decl_kernel<FRAME_, HALF_>), GRID_, BLK_, 0, s, c->arena, c->xy, ids, payload, \
                        off, len, n, c->capacity, c->err, c->sink, fa, cl, dg)
@@ -218,7 +210,7 @@ int launch_crypt(zrc4_ctx *c, int mode, const uint32_t *ids, uint32_t first_slot
     // Few whole groups: half-group workgroups, one per CU (2 waves per CU).
     // A grouped bucket's slots may sit in either half whatever its entry
     // count, so it always gets both halves.
-    const bool half = ZRC4_HALF && 2u * grid <= (uint32_t)c->num_cus &&
+    const bool half = 2u * grid <= (uint32_t)c->num_cus &&
                       ((mode == zrc4::kRange && (first_slot & 255u) == 0u) || mode == zrc4::kGrouped);
     if (half) {
         const dim3 hblk(zrc4::kHalfBlock);
@@ -1025,7 +1017,45 @@ const char *zrc4_strerror(int code)
     }
 }
 
-const char *zrc4_version(void) { return "zrc4-mi355x 0.2 (gfx950)"; }
+// The product's string, plus " [NAME=value]" for each of the five build knobs
+// (zsummerx_amd/build.py KEPT_KNOBS) that differs from its default, so that a
+// test or diagnostic library cannot pass for the product.  (The defaults are
+// repeated here from the knobs' #ifndef sites: tests/test_capi.py fails on
+// the product library if one of them moves alone.)
+#define ZRC4_STR2(x) #x
+#define ZRC4_STR(x) ZRC4_STR2(x)
+#define ZRC4_KNOB(NAME) " [" #NAME "=" ZRC4_STR(NAME) "]"
+#if ZRC4_TIMING != 0
+#define ZRC4_V_TIMING ZRC4_KNOB(ZRC4_TIMING)
+#else
+#define ZRC4_V_TIMING ""
+#endif
+#if ZRC4_WIN_TAG_LIMIT != (1u << 23)
+#define ZRC4_V_WIN_TAG_LIMIT ZRC4_KNOB(ZRC4_WIN_TAG_LIMIT)
+#else
+#define ZRC4_V_WIN_TAG_LIMIT ""
+#endif
+#if defined(ZRC4_TEST_HOOKS) && ZRC4_TEST_HOOKS
+#define ZRC4_V_TEST_HOOKS ZRC4_KNOB(ZRC4_TEST_HOOKS)
+#else
+#define ZRC4_V_TEST_HOOKS ""
+#endif
+#if ZRC4_GR_PRECLAIM_MAX != 64
+#define ZRC4_V_GR_PRECLAIM_MAX ZRC4_KNOB(ZRC4_GR_PRECLAIM_MAX)
+#else
+#define ZRC4_V_GR_PRECLAIM_MAX ""
+#endif
+#if ZRC4_STATES_GATHER_MAX != 4
+#define ZRC4_V_STATES_GATHER_MAX ZRC4_KNOB(ZRC4_STATES_GATHER_MAX)
+#else
+#define ZRC4_V_STATES_GATHER_MAX ""
+#endif
+
+const char *zrc4_version(void)
+{
+    return "zrc4-mi355x 0.2 (gfx950)" ZRC4_V_TIMING ZRC4_V_WIN_TAG_LIMIT ZRC4_V_TEST_HOOKS ZRC4_V_GR_PRECLAIM_MAX
+           ZRC4_V_STATES_GATHER_MAX;
+}
 
 #if ZRC4_TIMING
 // Diagnostic builds only: the per-wave timestamp records (zrc4_kernels.hpp,

@@ -348,7 +348,7 @@ __device__ __forceinline__ uint4 xor16(uint8_t *S, Rc4Lane &st, uint4 v)
     return v;
 }
 
-// Hand-written gfx950 step.  Each index update is ONE SDWA add that rewrites
+// Hand-written gfx950 step.  The y and t updates are ONE SDWA add that rewrites
 // byte 1 of an address register in place (dst_sel:BYTE_1, UNUSED_PRESERVE):
 // the mod-256 wrap is free and col (byte 0) is untouched.  The keystream byte
 // of step s is XORed into its payload byte at the end of step s+1 (its read
@@ -359,48 +359,23 @@ __device__ __forceinline__ uint4 xor16(uint8_t *S, Rc4Lane &st, uint4 v)
 // XC = address of S[x] for this step; XN = address of S[x+1], derived from XC
 // inside the step right before its read.  XC is free after the S[x] = b write.
 // Per byte: 4 VALU + 5 LDS + 2 waits.
-// x + 1: ZRC4_XADD16 (default) adds 0x100 (SGPR operand c100) with a 16-bit
-// add, whose wrap at 65 536 is the mod-256 wrap of byte 1 (XN and XC hold
-// the same col in byte 0, bits 16-31 stay zero): a 4-byte VOP2 encoding
-// instead of the 8-byte SDWA add.
-#ifndef ZRC4_XADD16
-#define ZRC4_XADD16 1
-#endif
-#if ZRC4_XADD16
-#define ZRC4_XINC(XC, XN) "v_add_u16_e32 %[" #XN "], %[c100], %[" #XC "]\n\t"
-#else
-#define ZRC4_XINC(XC, XN)                                                                        \
-    "v_add_u32_sdwa %[" #XN "], 1, %[" #XC "] dst_sel:BYTE_1 dst_unused:UNUSED_PRESERVE "        \
-    "src0_sel:DWORD src1_sel:BYTE_1\n\t"
-#endif
-// ZRC4_AB_LDS (timing-only ablations, outputs wrong): 1 drops the S[x] = b
-// write, 2 drops the keystream read S[t] -- how much the LDS pipe bounds the
-// step at 8 waves per CU.
-#ifndef ZRC4_AB_LDS
-#define ZRC4_AB_LDS 0
-#endif
-#if ZRC4_AB_LDS == 1
-#define ZRC4_CORE_XW(XC)
-#define ZRC4_CORE_KR(K) "s_waitcnt lgkmcnt(1)\n\t"
-#elif ZRC4_AB_LDS == 2
-#define ZRC4_CORE_XW(XC) "ds_write_b8 %[" #XC "], %[b]\n\t"
-#define ZRC4_CORE_KR(K) "s_waitcnt lgkmcnt(1)\n\t"
-#else
-#define ZRC4_CORE_XW(XC) "ds_write_b8 %[" #XC "], %[b]\n\t"
-#define ZRC4_CORE_KR(K) "ds_read_u8 %[" #K "], %[ta]\n\t" "s_waitcnt lgkmcnt(2)\n\t"
-#endif
+// x + 1 adds 0x100 (SGPR operand c100) with a 16-bit add, whose wrap at
+// 65 536 is the mod-256 wrap of byte 1 (XN and XC hold the same col in byte
+// 0, bits 16-31 stay zero): a 4-byte VOP2 encoding instead of the 8-byte SDWA
+// add.
 #define ZRC4_CORE(XC, XN, A, P, K)                                                               \
     "v_add_u32_sdwa %[ya], %[ya], %[" #A "] dst_sel:BYTE_1 dst_unused:UNUSED_PRESERVE "          \
     "src0_sel:BYTE_1 src1_sel:BYTE_0\n\t"                                                        \
     "ds_read_u8 %[b], %[ya]\n\t"                                                                 \
     "ds_write_b8 %[ya], %[" #A "]\n\t"                                                           \
-    ZRC4_XINC(XC, XN)                                                                            \
+    "v_add_u16_e32 %[" #XN "], %[c100], %[" #XC "]\n\t"                                          \
     "ds_read_u8 %[" #P "], %[" #XN "]\n\t"                                                       \
     "s_waitcnt lgkmcnt(2)\n\t"                                                                   \
-    ZRC4_CORE_XW(XC)                                                                             \
+    "ds_write_b8 %[" #XC "], %[b]\n\t"                                                           \
     "v_add_u32_sdwa %[ta], %[" #A "], %[b] dst_sel:BYTE_1 dst_unused:UNUSED_PRESERVE "           \
     "src0_sel:BYTE_0 src1_sel:BYTE_0\n\t"                                                        \
-    ZRC4_CORE_KR(K)
+    "ds_read_u8 %[" #K "], %[ta]\n\t"                                                            \
+    "s_waitcnt lgkmcnt(2)\n\t"
 
 #define ZRC4_E ZRC4_CORE(x0, x1, a0, a1, k0)   // even step: keystream -> k0
 #define ZRC4_O ZRC4_CORE(x1, x0, a1, a0, k1)   // odd step:  keystream -> k1
@@ -503,53 +478,6 @@ __device__ __forceinline__ uint32_t head_bytes(const uint8_t *msg, uint32_t len)
     "s_waitcnt vmcnt(8)\n\t"                                                                     \
     ZL_BLOCK(v56, v57, v58, v59, v60, v61, v62, v63, v64, v65, v66, v67, v68, v69, v70, v71)    \
     ZL_STORE(ZL_B0, ZL_B1, ZL_B2, ZL_B3)
-// ZRC4_BLK_DEFER (A/B, default 0 = the ISA above): each block's keystream
-// goes into K first (byte moves, as block 0's does) and the wait for the
-// block's payload comes after it, so a block's loads have two blocks of
-// keystream time to land instead of one (+16 VALU per block for the XOR).
-#ifndef ZRC4_BLK_DEFER
-#define ZRC4_BLK_DEFER 0
-#endif
-#define ZL_MOVK(R, SEL, K)                                                                       \
-    "v_mov_b32_sdwa " #R ", %[" #K "] dst_sel:" #SEL " dst_unused:UNUSED_PRESERVE src0_sel:BYTE_0\n\t"
-#define ZL_W0K(D)                                                                                \
-    ZRC4_E ZRC4_O ZL_MOVK(D, BYTE_0, k0) ZRC4_E ZL_MOVK(D, BYTE_1, k1)                          \
-    ZRC4_O ZL_MOVK(D, BYTE_2, k0)
-#define ZL_WK(DP, D)                                                                             \
-    ZRC4_E ZL_MOVK(DP, BYTE_3, k1) ZRC4_O ZL_MOVK(D, BYTE_0, k0)                                \
-    ZRC4_E ZL_MOVK(D, BYTE_1, k1) ZRC4_O ZL_MOVK(D, BYTE_2, k0)
-#define ZL_BLOCKK                                                                                \
-    ZL_W0K(v72) ZL_WK(v72, v73) ZL_WK(v73, v74) ZL_WK(v74, v75) ZL_WK(v75, v76) ZL_WK(v76, v77)   \
-    ZL_WK(v77, v78) ZL_WK(v78, v79) ZL_WK(v79, v80) ZL_WK(v80, v81) ZL_WK(v81, v82)               \
-    ZL_WK(v82, v83) ZL_WK(v83, v84) ZL_WK(v84, v85) ZL_WK(v85, v86) ZL_WK(v86, v87)               \
-    "s_waitcnt lgkmcnt(0)\n\t" ZL_MOVK(v87, BYTE_3, k1)
-#define ZL_KXOR(d0, d1, d2, d3, d4, d5, d6, d7, d8, d9, d10, d11, d12, d13, d14, d15)            \
-    "v_xor_b32_e32 " #d0 ", " #d0 ", v72\n\tv_xor_b32_e32 " #d1 ", " #d1 ", v73\n\t"                 \
-    "v_xor_b32_e32 " #d2 ", " #d2 ", v74\n\tv_xor_b32_e32 " #d3 ", " #d3 ", v75\n\t"                 \
-    "v_xor_b32_e32 " #d4 ", " #d4 ", v76\n\tv_xor_b32_e32 " #d5 ", " #d5 ", v77\n\t"                 \
-    "v_xor_b32_e32 " #d6 ", " #d6 ", v78\n\tv_xor_b32_e32 " #d7 ", " #d7 ", v79\n\t"                 \
-    "v_xor_b32_e32 " #d8 ", " #d8 ", v80\n\tv_xor_b32_e32 " #d9 ", " #d9 ", v81\n\t"                 \
-    "v_xor_b32_e32 " #d10 ", " #d10 ", v82\n\tv_xor_b32_e32 " #d11 ", " #d11 ", v83\n\t"             \
-    "v_xor_b32_e32 " #d12 ", " #d12 ", v84\n\tv_xor_b32_e32 " #d13 ", " #d13 ", v85\n\t"             \
-    "v_xor_b32_e32 " #d14 ", " #d14 ", v86\n\tv_xor_b32_e32 " #d15 ", " #d15 ", v87\n\t"
-#if ZRC4_BLK_DEFER
-#undef ZL_HALF_A
-#undef ZL_HALF_B
-#define ZL_HALF_A                                                                                \
-    ZL_ACTIVE                                                                                    \
-    ZL_PREFETCH(ZL_B0, ZL_B1, ZL_B2, ZL_B3)                                                      \
-    ZL_BLOCKK                                                                                    \
-    "s_waitcnt vmcnt(8)\n\t"                                                                     \
-    ZL_KXOR(v40, v41, v42, v43, v44, v45, v46, v47, v48, v49, v50, v51, v52, v53, v54, v55)     \
-    ZL_STORE(ZL_A0, ZL_A1, ZL_A2, ZL_A3)
-#define ZL_HALF_B                                                                                \
-    ZL_ACTIVE                                                                                    \
-    ZL_PREFETCH(ZL_A0, ZL_A1, ZL_A2, ZL_A3)                                                      \
-    ZL_BLOCKK                                                                                    \
-    "s_waitcnt vmcnt(8)\n\t"                                                                     \
-    ZL_KXOR(v56, v57, v58, v59, v60, v61, v62, v63, v64, v65, v66, v67, v68, v69, v70, v71)     \
-    ZL_STORE(ZL_B0, ZL_B1, ZL_B2, ZL_B3)
-#endif
 #define ZL_FIRST                                                                                 \
     "s_mov_b32 %[i], 0\n\t"                                                                      \
     ZL_PREFETCH(ZL_B0, ZL_B1, ZL_B2, ZL_B3)                                                      \
@@ -682,22 +610,16 @@ typedef uint32_t u32x16 __attribute__((ext_vector_type(16)));
 typedef uint32_t u32x32 __attribute__((ext_vector_type(32)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
-// ZRC4_PRIO (crypt_stream_kernel): the two workgroups of a CU share its SIMDs
-// (one wave of each per SIMD) and the older wave wins the issue arbitration,
-// so one workgroup runs ahead (a CU's two workgroups differ by up to 7 us per
-// group, profiles/r02/stream_tl_pairs.log) and the other finishes alone at the
-// 4-wave rate.  1: alternate which of a SIMD's two waves (wave slot parity,
-// HW_ID) has the higher priority from one group to the next (cfg5 288.4 ->
-// 284.2 us; alternating every line-loop half: 286.3, profiles/r02/ab_prio.log).
-#ifndef ZRC4_PRIO
-#define ZRC4_PRIO 1
-#endif
+// Wave priority (crypt_stream_kernel): the two workgroups of a CU share its
+// SIMDs (one wave of each per SIMD) and the older wave wins the issue
+// arbitration, so one workgroup runs ahead (a CU's two workgroups differ by up
+// to 7 us per group, profiles/r02/stream_tl_pairs.log) and the other finishes
+// alone at the 4-wave rate.  The kernel therefore alternates which of a SIMD's
+// two waves (wave slot parity, HW_ID) has the higher priority from one group
+// to the next (cfg5 288.4 -> 284.2 us; alternating every line-loop half:
+// 286.3, profiles/r02/ab_prio.log).
 
-#if defined(ZRC4_LL_AB) && ZRC4_LL_AB
-#include "ab/zrc4_line_loop_ab.inc"   // timing-only A/B builds (tools/ab_bench.py --no-check)
-#else
 #include "zrc4_line_loop.inc"
-#endif
 
 constexpr uint32_t kSinkSlot = 256;                 // bytes of sink per thread (128-B line + offsets)
 constexpr uint32_t kSinkBytes = kGroup * kSinkSlot  // one 64 KiB sink per context, shared by all workgroups
@@ -757,43 +679,19 @@ __device__ __forceinline__ void line_roles(u32x16 &addr, u32x8 &lim, const LineS
 }
 
 // Line 0 (the lane's own blocks 0, 1; the sink past the session's end): the
-// compiler's loads, retired before the S-box fill.
+// compiler's loads, retired before the S-box fill.  The persistent kernel
+// also loads the next group's line 0 this way after the keystream, and the
+// compiler then drains everything (vmcnt(0), the 16 image stores included)
+// after the next fill.  Issuing that line from asm with a counted vmcnt(16)
+// was no faster (same-process medians, profiles/r04/grp/ab_range.log,
+// ab_grouped.log: cfg5 287.2 vs 286.2 us, grouped cfg5 298.0 vs 296.4; most
+// 1 KiB groups load line 0 inside the last half, p_async), so the simpler
+// compiler form stays.
 __device__ __forceinline__ void preload_line0(u32x32 &P, const LineSetup &ls, const uint8_t *sk)
 {
     const uint8_t *p = reinterpret_cast<const uint8_t *>((uintptr_t)ls.p);
     const uint32_t nb = ls.nblk;
     preload_line(P, nb > 0 ? p : sk, nb > 1 ? p + 64 : sk + 64);
-}
-
-// Line 0 of the next group from asm (ZRC4_LINE0_ASM, r04 A/B knob, off):
-// issued after the keystream, before the image copy-out, and waited for
-// after the next fill with a counted vmcnt(16) (the 16 image stores are the
-// only younger VMEM ops); as compiler loads the compiler drains everything
-// there (vmcnt(0)), the image stores included.  Same-process medians
-// (profiles/r04/grp/ab_range.log, ab_grouped.log): cfg5 287.2 vs 286.2 us,
-// grouped cfg5 298.0 vs 296.4 -- the drain costs nothing measurable (most
-// 1 KiB groups load line 0 inside the last half, p_async), so the simpler
-// compiler form stays.
-#ifndef ZRC4_LINE0_ASM
-#define ZRC4_LINE0_ASM 0
-#endif
-__device__ __forceinline__ void issue_line0_asm(u32x32 &P, const LineSetup &ls, const uint8_t *sk)
-{
-    const uint8_t *p = reinterpret_cast<const uint8_t *>((uintptr_t)ls.p);
-    const uint32_t nb = ls.nblk;
-    const uint8_t *b0 = nb > 0 ? p : sk, *b1 = nb > 1 ? p + 64 : sk + 64;
-    asm volatile(
-        "global_load_dwordx4 v[40:43], %[a0], off\n\t"
-        "global_load_dwordx4 v[44:47], %[a0], off offset:16\n\t"
-        "global_load_dwordx4 v[48:51], %[a0], off offset:32\n\t"
-        "global_load_dwordx4 v[52:55], %[a0], off offset:48\n\t"
-        "global_load_dwordx4 v[56:59], %[a1], off\n\t"
-        "global_load_dwordx4 v[60:63], %[a1], off offset:16\n\t"
-        "global_load_dwordx4 v[64:67], %[a1], off offset:32\n\t"
-        "global_load_dwordx4 v[68:71], %[a1], off offset:48\n\t"
-        : "=&{v[40:71]}"(P)
-        : [a0] "v"(b0), [a1] "v"(b1)
-        : "memory");
 }
 
 // Line 1 (blocks 2, 3), issued from asm after the S-box fill, so it is in
@@ -1299,55 +1197,23 @@ __device__ __forceinline__ void frame_walk_chunks(const uint8_t *payload, const 
 // addresses), then 16 B of flags, then the kGrouped entry table (slot -> entry
 // index / length / offset).  HALF pads the allocation past 80 KiB so that a
 // CU holds one workgroup.
-#ifndef ZRC4_HALF_PAD
-#define ZRC4_HALF_PAD 1
-#endif
-#ifndef ZRC4_WPERM
-#define ZRC4_WPERM 97
-#endif
-#ifndef ZRC4_WMAP
-#define ZRC4_WMAP 1
-#endif
 constexpr uint32_t kTabOff = kGroupBytes + 16;
 constexpr uint32_t kSidOff = kTabOff + 256 * 16;              // 16 B: the half-group workgroup's SIMD ids
 constexpr uint32_t kSmemDirect = kSidOff + 16;                // 69 664 B: two workgroups per CU
 constexpr uint32_t kSmemHalf = 96 * 1024;                     // one workgroup per CU
 
 // Workgroup k runs on XCD k mod 8.  xcd_run_map deals the groups so that
-// each XCD takes runs of R = ZRC4_XCD_RUN consecutive groups per 8R: k =
+// each XCD takes runs of R = kXcdRun consecutive groups per 8R: k =
 // 8R s + 8 r + x -> 8R s + R x + r (bijective; a tail of grid mod 8R groups
 // keeps its order; R = 1 is the identity).
-#ifndef ZRC4_XCD_RUN
-#define ZRC4_XCD_RUN 8
-#endif
-static_assert(ZRC4_XCD_RUN >= 1 && ZRC4_XCD_RUN <= 32 && (ZRC4_XCD_RUN & (ZRC4_XCD_RUN - 1)) == 0,
+constexpr uint32_t kXcdRun = 8;
+static_assert(kXcdRun >= 1 && kXcdRun <= 32 && (kXcdRun & (kXcdRun - 1)) == 0,
               "XCD run length: a power of two");
 __device__ __forceinline__ uint32_t xcd_run_map(uint32_t k, uint32_t grid)
 {
-    constexpr uint32_t R = ZRC4_XCD_RUN, B = 8u * R;
+    constexpr uint32_t R = kXcdRun, B = 8u * R;
     if (k >= (grid & ~(B - 1u))) return k;
     return (k & ~(B - 1u)) | ((k & 7u) * R) | ((k >> 3) & (R - 1u));
-}
-
-// ZRC4_PAIR_DIRECT: whole-group range launches (crypt_kernel<kRange>) by
-// wave pairs as the persistent kernel (pair_meet, img_vo): each pair fills,
-// runs and copies out its half image without waiting for the other.
-// Measured, not kept: with one group per workgroup there is no boundary to
-// decouple, only the fill and the end (same process,
-// profiles/r04/pdirect/ab_direct.log: cfg3 25.50 vs 25.32 us with the
-// barriers, 65 536 x 1 KiB 58.44 vs 58.24, x 512 B 36.60 vs 36.32).
-#ifndef ZRC4_PAIR_DIRECT
-#define ZRC4_PAIR_DIRECT 0
-#endif
-__device__ __forceinline__ void pair_meet_d(uint32_t *ctr, uint32_t &gen)
-{
-    ++gen;
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    if ((threadIdx.x & 63u) == 0u) __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    while (__builtin_amdgcn_readfirstlane(__hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) <
-           2u * gen)
-        __builtin_amdgcn_s_sleep(1);
-    asm volatile("" ::: "memory");
 }
 
 // Declared bucket groups of a grouped launch of at most 256 buckets on the
@@ -1378,7 +1244,7 @@ crypt_body(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy,
 
     constexpr uint32_t kLanes = HALF ? 128u : 256u;
     uint32_t tid = threadIdx.x;
-    if constexpr (HALF && ZRC4_HALF_PAD) {
+    if constexpr (HALF) {
         // The workgroup has 4 waves; the two that work are the ones on SIMDs
         // 1 and 2 (else 1 and 3).  Measured per wave (in-kernel clocks,
         // tools/kernel_timeline.py --placement, profiles/r02/placement_*.log):
@@ -1408,8 +1274,8 @@ crypt_body(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy,
     }
     // Which group (bucket) this workgroup runs.  Whole-group launches deal
     // the groups to the XCDs in runs of 8 consecutive groups (xcd_run_map,
-    // ZRC4_WMAP, r03): with workgroup k -> group k (or r02's 97k mod grid,
-    // ZRC4_WMAP=0) XCD x ran only the groups = x mod 8, whose payload and
+    // r03): with workgroup k -> group k (or r02's 97k mod grid) XCD x ran
+    // only the groups = x mod 8, whose payload and
     // images sit at one offset modulo 8 groups, and the XCD's L2 evicted the
     // lanes' partly written 128-byte lines early: 1.25x the algorithmic write
     // bytes at 256-byte messages, 1.00x with the runs; 65 536 x 1 KiB 60.5 ->
@@ -1417,33 +1283,12 @@ crypt_body(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy,
     // medians, profiles/r03/wmap/).  Half-group launches keep k -> (k/2, k%2)
     // (their A/B was neutral to +2.5 %).
     uint32_t wg = blockIdx.x;
-#if ZRC4_WMAP
     if constexpr (!HALF) wg = xcd_run_map(blockIdx.x, gridDim.x);
-#else
-    if constexpr (!HALF && ZRC4_WPERM != 0) {
-        constexpr uint32_t kMul = ZRC4_WPERM + 0u;
-        if (gridDim.x % kMul != 0u) wg = (blockIdx.x * kMul) % gridDim.x;
-    }
-#endif
-#if defined(ZRC4_STAGGER) && ZRC4_STAGGER
-    // A/B diagnostic (cfg3 write traffic): workgroup start spread over
-    // 0..7 x ZRC4_STAGGER x 64 cycles, as a grouped launch's longer prologue spreads it
-    if constexpr (MODE == kRange && !HALF)
-        for (uint32_t i = 0; i < (blockIdx.x & 7u); ++i) __builtin_amdgcn_s_sleep(ZRC4_STAGGER);
-#endif
     const uint32_t e = wg * kLanes + tid;                // batch entry of this thread
     const bool valid = e < n;
     const uint32_t h = HALF ? (wg & 1u) : 0u;            // half of the group (HALF)
     const uint32_t j = h * 128u + tid;                   // group lane
-    // (range whole groups by pairs: thread j's chunks sit in its pair's half rows)
-    constexpr bool PD = MODE == kRange && !HALF && ZRC4_PAIR_DIRECT;
-    const uint32_t vo0 = PD ? image_lane_offset(tid & 127u, true, tid >> 7) : image_lane_offset(tid, HALF, h);
-    uint32_t *pdc = reinterpret_cast<uint32_t *>(smem + kGroupBytes) + 4u + __builtin_amdgcn_readfirstlane(tid >> 7);
-    uint32_t pdg = 0;
-    if constexpr (PD) {
-        if (tid < 2u) reinterpret_cast<uint32_t *>(smem + kGroupBytes)[4u + tid] = 0u;
-        __syncthreads();
-    }
+    const uint32_t vo0 = image_lane_offset(tid, HALF, h);
     const uint32_t col = col_of(j);
     // (plain LDS words, ordered by the barriers: as `volatile` they compiled
     // to flat stores with a vmcnt(0) after each, which drained the grouped
@@ -1672,8 +1517,7 @@ crypt_body(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy,
         if (pre) issue_block_asm(A, msg);
 #pragma unroll
         for (int i = 0; i < 16; ++i) *reinterpret_cast<uint4 *>(S + i * 4096 + vo0) = img[i];
-        if constexpr (PD) pair_meet_d(pdc, pdg);
-        else __syncthreads();
+        __syncthreads();
         if constexpr (MODE == kGrouped) {
             if (flag[3]) {                               // another bucket of this launch holds the group
                 if (tid == 0) latch_fault(err, kErrGroup);
@@ -1705,8 +1549,7 @@ crypt_body(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy,
     stamp(ts, 2);
 
     if (whole) {
-        if constexpr (PD) pair_meet_d(pdc, pdg);
-        else __syncthreads();
+        __syncthreads();
         uint8_t *img_out = arena + (size_t)g * kGroupBytes;
 #pragma unroll
         for (int i = 0; i < 16; ++i)
@@ -1736,7 +1579,7 @@ crypt_kernel(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy,
 // The grouped forms with declared bucket groups (zrc4_crypt_grouped_declared,
 // 33..256 buckets): the groups in the kernel arguments.
 template <bool FRAME, bool HALF>
-__global__ void __launch_bounds__(HALF ? (ZRC4_HALF_PAD ? 256u : 128u) : 256u, HALF ? 1 : 2)
+__global__ void __launch_bounds__(256u, HALF ? 1 : 2)
 crypt_decl_kernel(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy,
                   const uint32_t *__restrict__ ids, uint8_t *__restrict__ payload,
                   const uint64_t *__restrict__ off, const uint32_t *__restrict__ len, uint32_t n,
@@ -1748,10 +1591,9 @@ crypt_decl_kernel(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy,
 }
 
 // Half-group workgroups (kRange / kGrouped, few groups): one per CU;
-// workgroup 2w + h runs half h of bucket w.  ZRC4_HALF_PAD: launched with 256
-// threads, of which the two waves that work are picked by SIMD (crypt_body);
-// A/B knob: 0 launches 128 threads.
-constexpr uint32_t kHalfBlock = ZRC4_HALF_PAD ? 256u : 128u;
+// workgroup 2w + h runs half h of bucket w.  Launched with 256 threads, of
+// which the two waves that work are picked by SIMD (crypt_body).
+constexpr uint32_t kHalfBlock = 256u;
 
 template <int MODE, bool FRAME = false>
 __global__ void __launch_bounds__(kHalfBlock, 1)
@@ -1898,12 +1740,11 @@ __device__ __forceinline__ void prefetch_group(u32x32 &P, u32x32 &Q, u32x32 &ilo
 constexpr uint32_t kGrVote = 0;                          // 4 waves x {guess, bad}
 constexpr uint32_t kGrLost = 8;                          // the current bucket's claim was lost
 constexpr uint32_t kGrTab = 16;                          // slot & 255 -> entry index
-constexpr uint32_t kSmemStreamGr = kGroupBytes + 4u * (kGrTab + 256u);   // 66 624 B: two workgroups per CU
 
 // The table of bucket nb from its raw entries (thread j holds entry nb*256 +
 // j), plus this wave's vote.  Call between two barriers that order it after
 // every read of the previous table.
-// lo (ZRC4_GR_FASTPRO prologue): each busy entry also leaves its length at
+// lo (the pair kernel's prologue): each busy entry also leaves its length at
 // lo[slot & 255] and its offset at lo + 256 (u64) -- the permuted entry the
 // lane of that column would otherwise gather from HBM.
 __device__ __forceinline__ void bucket_table(uint32_t *gr, uint32_t nb, uint32_t id, uint32_t ln, uint32_t n,
@@ -1968,7 +1809,7 @@ __device__ __forceinline__ BucketView bucket_read(const uint32_t *gr, uint32_t n
     return bv;
 }
 
-// Grouped buckets with wave pairs (ZRC4_PAIR): each pair (waves 2p, 2p+1)
+// Grouped buckets with wave pairs: each pair (waves 2p, 2p+1)
 // runs its half of every bucket on its own schedule, so it keeps its own
 // votes / claim-lost word / table (region p, kGrPairWords words), claims
 // its own part p of the group (so two buckets naming one group can only
@@ -1984,13 +1825,10 @@ constexpr uint32_t kGrPairWords = kGrPairCnt + 512u;      // votes, lost, table,
 constexpr uint32_t kGrMeet = 2u * kGrPairWords;           // 2 pair-meet counters
 constexpr uint32_t kGrCnt = kGrMeet + 2u;                 // 2 boundaries-done counters
 constexpr uint32_t kGrStg = kGrCnt + 2u;                  // 2 x 256 raw entries {id, len}
-// ZRC4_GR_FASTPRO: the first bucket's permuted lengths (256 words) and
-// offsets (256 u64), written with its table in the prologue
-#ifndef ZRC4_GR_FASTPRO
-#define ZRC4_GR_FASTPRO 1
-#endif
+// then the first bucket's permuted lengths (256 words) and offsets (256 u64),
+// written with its table in the prologue
 constexpr uint32_t kGrPro = kGrStg + 1024u;
-constexpr uint32_t kSmemStreamGrPair = kGroupBytes + 4u * (kGrPro + (ZRC4_GR_FASTPRO ? 768u : 0u));   // 78 992 B: two workgroups per CU
+constexpr uint32_t kSmemStreamGrPair = kGroupBytes + 4u * (kGrPro + 768u);   // 78 992 B: two workgroups per CU
 
 // Pair version of the bucket table, in two halves around the pair's meet
 // so that a boundary pays two LDS round trips (each one queues behind the
@@ -2093,11 +1931,10 @@ __device__ __forceinline__ BucketView bucket_read_pair(const uint32_t *grp, cons
     return bv;
 }
 
-#ifndef ZRC4_GR_PRECLAIM
-#define ZRC4_GR_PRECLAIM 1       // the pair kernel claims the groups of its first buckets in the prologue
-#endif
+// The pair kernel claims the groups of its first buckets in the prologue:
+// this many of them (the lost mask is 64 bits; a test build uses 1).
 #ifndef ZRC4_GR_PRECLAIM_MAX
-#define ZRC4_GR_PRECLAIM_MAX 64  // how many (the lost mask is 64 bits; a test build uses 1)
+#define ZRC4_GR_PRECLAIM_MAX 64
 #endif
 static_assert(ZRC4_GR_PRECLAIM_MAX >= 1 && ZRC4_GR_PRECLAIM_MAX <= 64, "pre-claim mask is 64 bits");
 // The next bucket's claim (lane 0 of wave 0 swaps the launch epoch into the
@@ -2237,17 +2074,14 @@ __device__ __forceinline__ void lds_to_image_asm(uint8_t *img, uint32_t tid)
         : "memory");
 }
 
-// ZRC4_PAIR (the range form of crypt_stream_kernel): the two wave pairs of a
+// The prefetching forms of crypt_stream_kernel: the two wave pairs of a
 // workgroup run their groups decoupled.  Pair p (waves 2p, 2p+1) owns the
 // columns with bit 7 = p, i.e. bytes [128p, 128p + 128) of every image row,
 // and moves exactly those (img_vo), so at a group boundary its waves only
 // wait for each other: they meet through an LDS counter instead of the
-// workgroup barrier.  Measured first as a timing-only ablation with whole
-// images (pair meets, outputs wrong): cfg5 284.5 -> 276.3 us, 262 144 x 1 KiB
-// 151.3 -> 148.7 (profiles/r04/ab/ab_pair.log).  0: workgroup barriers.
-#ifndef ZRC4_PAIR
-#define ZRC4_PAIR 1
-#endif
+// workgroup barrier.  Measured before it was built, as a timing run with pair
+// meets over whole images (its ciphertext was not valid): cfg5 284.5 -> 276.3
+// us, 262 144 x 1 KiB 151.3 -> 148.7 (profiles/r04/ab/ab_pair.log).
 __device__ __forceinline__ void pair_meet(uint32_t *ctr, uint32_t &gen)
 {
     ++gen;
@@ -2269,8 +2103,7 @@ crypt_stream_kernel(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy,
                     FrameArgs fr = FrameArgs{})
 {
     static_assert(PF || !GR, "grouped batches run the prefetching form");
-    constexpr bool PG = GR && ZRC4_PAIR;       // grouped buckets by wave pairs
-    __shared__ __attribute__((aligned(16))) uint8_t smem[GR ? (PG ? kSmemStreamGrPair : kSmemStreamGr) : kGroupBytes + 16];
+    __shared__ __attribute__((aligned(16))) uint8_t smem[GR ? kSmemStreamGrPair : kGroupBytes + 16];
     uint8_t *S = smem;
     if (!lds_base_ok(S, err)) return;
     uint32_t *gr = reinterpret_cast<uint32_t *>(smem + kGroupBytes);    // GR: votes, claim word, table
@@ -2284,17 +2117,15 @@ crypt_stream_kernel(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy,
 
     uint32_t w = blockIdx.x;
     const uint32_t pr = __builtin_amdgcn_readfirstlane(j >> 7);   // this wave's pair (an SGPR)
-#if ZRC4_PAIR
     uint32_t *pctr = gr + (GR ? kGrMeet : 0u) + pr;         // this pair's meet counter
     uint32_t pgen = 0;                                      // meetings so far
     if constexpr (PF && !GR) {
         if (j < 2u) gr[j] = 0u;
         __syncthreads();
     }
-#endif
-    // PG: this pair's region, the staging buffers, boundaries done so far;
+    // GR: this pair's region, the staging buffers, boundaries done so far;
     // the next bucket's vote (before the meet) and view (after it)
-    uint32_t *grp = gr + (PG ? pr * kGrPairWords : 0u);
+    uint32_t *grp = gr + (GR ? pr * kGrPairWords : 0u);
     uint32_t bk = 0;
     EntryIn cur;
     u32x32 ilo, ihi;                          // PF: this group's image, 16 x 16 B per lane
@@ -2318,10 +2149,10 @@ crypt_stream_kernel(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy,
     uint32_t gcur = 0;
     bool cur_ok = false;
     uint32_t cold = 0;
-    uint64_t lostm = 0;                       // PG + ZRC4_GR_PRECLAIM: bucket k's claim lost (k < 64)
+    uint64_t lostm = 0;                       // GR: bucket k's pre-claim lost (k < 64)
     bool pre = false;                         // ... pre-claims on (wave-uniform)
     uint32_t qid = ZRC4_INVALID, qlen = 0;
-    if constexpr (PG) {
+    if constexpr (GR) {
         // Prologue (whole workgroup): bucket w's table in pair 0's region,
         // each pair's claim on its part, the permuted entry, x/y and image;
         // bucket w + grid's raw entries into staging buffer 1 (the table of
@@ -2342,7 +2173,7 @@ crypt_stream_kernel(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy,
         // us) and lose below (262 144 / 131 072 x 1 KiB, 2 / 1 bucket: +1.5 /
         // +2.4 us; profiles/r04/claim3), where bucket 0 claims in the prologue
         // and later ones in the loop, as without them.
-        pre = ZRC4_GR_PRECLAIM && KB >= 3u;
+        pre = KB >= 3u;
         const uint32_t wv = __builtin_amdgcn_readfirstlane(j >> 6);
         uint32_t idk[8], lk[8];
         // (unconditional loads from a clamped entry, selected afterwards: a
@@ -2364,15 +2195,12 @@ crypt_stream_kernel(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy,
         }
         qid = idk[2];
         qlen = lk[2];
-#if ZRC4_GR_FASTPRO
         // Bucket 0's offsets with its ids: its table hands each column its
         // length and offset through LDS, so line 0 needs no gather round trip
         // (the image itself waits for the table: issued before the claims, its
         // loads would be drained by the wait for the claims' answers)
         const uint64_t of0 = off[w * kGroup + j < n ? w * kGroup + j : n - 1u];   // (unused past n)
-#endif
         *reinterpret_cast<uint2 *>(gr + kGrStg + 512u + 2u * j) = make_uint2(idk[1], lk[1]);
-#if ZRC4_GR_PRECLAIM
         // Claims up front: each of this workgroup's first 64 buckets whose
         // busy entries all name one group claims that group here -- one
         // atomic per bucket and pair, all in flight together; an atomic
@@ -2421,21 +2249,13 @@ crypt_stream_kernel(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy,
             if ((j & 127u) == 0u) grp[12] = (uint32_t)lb;
         };
         if (pre) votes(idk, lk);
-#endif
         __syncthreads();
-#if ZRC4_GR_FASTPRO
         bucket_table(gr, w, idk[0], lk[0], n, capacity, err, gr + kGrPro, of0);
-#else
-        bucket_table(gr, w, idk[0], lk[0], n, capacity, err);
-#endif
-#if ZRC4_GR_PRECLAIM
         if (pre) mixed(idk, lk);
-#endif
         __syncthreads();
         const BucketView bv = bucket_read(gr, w, err);
         gcur = bv.g;
         cur_ok = bv.ok;
-#if ZRC4_GR_PRECLAIM
         // (batch 0's answers are collected after the image loads are issued)
         uint32_t old0 = pre ? claim(0u) : 0u;
         if (!pre && bv.ok && (j & 127u) == 0u)
@@ -2471,12 +2291,6 @@ crypt_stream_kernel(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy,
                 lostm |= (uint64_t)__builtin_amdgcn_readfirstlane(grp[12]) << k0;
             }
         }
-#else
-        if (bv.ok && (j & 127u) == 0u)
-            cold = __hip_atomic_exchange(reinterpret_cast<uint32_t *>(cl.word + (size_t)bv.g * kClaimParts + (j >> 7)) + 1,
-                                         cl.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
-#if ZRC4_GR_FASTPRO
         cur.len = bv.valid ? gr[kGrPro + j] : 0u;
         cur.off = bv.valid ? reinterpret_cast<const uint64_t *>(gr + kGrPro + 256u)[j] : 0u;
         cur.slot = bv.valid ? bv.g * 256u + j : ZRC4_INVALID;
@@ -2488,65 +2302,17 @@ crypt_stream_kernel(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy,
         preload_line0(P, ls, sk);
         // the claims' answers after these loads: compared earlier, the wait
         // for them would drain the loads issued behind them
-#if ZRC4_GR_PRECLAIM
         asm volatile("" : "+v"(old0) :: "memory");
-#else
-        asm volatile("" ::: "memory");
-#endif
-#else
-        cur.len = bv.valid ? len[bv.ent] : 0u;
-        cur.off = bv.valid ? off[bv.ent] : 0u;
-        cur.slot = bv.valid ? bv.g * 256u + j : ZRC4_INVALID;
-        cur.xy = xy[bv.g * 256u + j];
-        load_image(gcur);                     // with the entry gathers, not after the barrier
-#endif
-#if ZRC4_GR_PRECLAIM
         if (pre && K <= 8u) lost_to_lds(old0);
-#endif
         __syncthreads();                      // table and votes read before the pairs build their own
-#if ZRC4_GR_PRECLAIM
         if (pre && K <= 8u) lostm = __builtin_amdgcn_readfirstlane(grp[12]);
-#endif
-    } else if constexpr (GR) {
-        // Prologue: bucket w's table (compiler loads, waited for once below),
-        // its claim, permuted entry, x/y and image; bucket w + grid's raw entry.
-        gr[kGrTab + j] = ZRC4_INVALID;
-        const uint32_t e0 = w * kGroup + j, e1 = (w + gridDim.x) * kGroup + j;
-        const uint32_t id0 = e0 < n ? ids[e0] : ZRC4_INVALID, l0 = e0 < n ? len[e0] : 0u;
-        if (e1 < n) {
-            qid = ids[e1];
-            qlen = len[e1];
-        }
-        __syncthreads();
-        bucket_table(gr, w, id0, l0, n, capacity, err);
-        __syncthreads();
-        const BucketView bv = bucket_read(gr, w, err);
-        gcur = bv.g;
-        cur_ok = bv.ok;
-        if (bv.ok && j == 0u)
-            cold = __hip_atomic_exchange(reinterpret_cast<uint32_t *>(cl.word + (size_t)bv.g * kClaimParts) + 1,
-                                         cl.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        cur.len = bv.valid ? len[bv.ent] : 0u;
-        cur.off = bv.valid ? off[bv.ent] : 0u;
-        cur.slot = bv.valid ? bv.g * 256u + j : ZRC4_INVALID;
-        cur.xy = xy[bv.g * 256u + j];
-        load_image(gcur);                     // with the entry gathers, not after the barrier
-        __syncthreads();                      // table and votes read before the next bucket's are built
     } else {
         load_entry(cur, w, j, ids, first_slot, off, len, n, capacity, err, xy);
     }
-#ifndef ZRC4_AB_NOIMG0
-#define ZRC4_AB_NOIMG0 0     // timing-only ablation: the first group's image is never loaded (outputs wrong)
-#endif
     if constexpr (PF && !GR) {
-        if constexpr (ZRC4_AB_NOIMG0) {
-#pragma unroll
-            for (int i = 0; i < 32; ++i) ilo[i] = ihi[i] = 0u;
-        } else {
-            load_image((first_slot >> 8) + w);
-        }
+        load_image((first_slot >> 8) + w);
     }
-    if constexpr (!PG || !ZRC4_GR_FASTPRO) {
+    if constexpr (!GR) {                      // (GR: in the prologue, behind the claims)
         line_setup(ls, payload + cur.off, cur.len);
         preload_line0(P, ls, sk);
     }
@@ -2577,7 +2343,7 @@ crypt_stream_kernel(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy,
                     u32x4{ihi[4 * i], ihi[4 * i + 1], ihi[4 * i + 2], ihi[4 * i + 3]};
             }
             asm volatile("" ::: "memory");        // the image is in LDS (its registers free) before the tables
-            if constexpr (PG) {
+            if constexpr (GR) {
                 // this pair's claim on the bucket; the next bucket's table
                 // from both pairs' raw entries (staging (bk + 1) & 1) once the
                 // other pair has finished boundary bk - 1, then bucket
@@ -2595,29 +2361,17 @@ crypt_stream_kernel(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy,
                 const bool qv = (w + 2u * gridDim.x) * kGroup + j < n;
                 *reinterpret_cast<uint2 *>(gr + kGrStg + 512u * (bk & 1u) + 2u * j) =
                     make_uint2(qv ? qid : ZRC4_INVALID, qlen);
-            } else if constexpr (GR) {
-                // this bucket's claim (read back with the entries), and the
-                // table of the bucket after next from its raw entries
-                if (j == 0u) gr[kGrLost] = cur_ok && cold == cl.epoch ? 1u : 0u;
-                if (w + gridDim.x < nwg) bucket_table(gr, w + gridDim.x, qid, qlen, n, capacity, err);
             }
-#if ZRC4_PAIR
-            if constexpr (!GR || PG) pair_meet(pctr, pgen); else
-#endif
-            __syncthreads();
-            uint32_t lostv = 0;
-            if constexpr (PG) {
+            pair_meet(pctr, pgen);
+            if constexpr (GR) {
                 // both waves are past their staging accesses of boundary bk
                 if ((j & 127u) == 0u)
                     __hip_atomic_fetch_add(gr + kGrCnt + pr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 ++bk;
-                lostv = __builtin_amdgcn_readfirstlane(grp[kGrLost]);
-            }
-            if constexpr (GR) {
-                const uint32_t lost = PG ? lostv : __builtin_amdgcn_readfirstlane(grp[kGrLost]);
+                const uint32_t lost = __builtin_amdgcn_readfirstlane(grp[kGrLost]);
                 if (cur_ok && lost != 0u) {
                     // another bucket of this launch holds the group: skip this one whole
-                    if ((j & (PG ? 127u : 255u)) == 0u) latch_fault(err, kErrGroup);
+                    if ((j & 127u) == 0u) latch_fault(err, kErrGroup);
                     cur_ok = false;
                     whole = false;
                     cur.len = 0u;
@@ -2662,36 +2416,25 @@ crypt_stream_kernel(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy,
         // image's stores are younger); past this point it is asm-defined, so
         // nothing the compiler tracks is pending at the loop.  Line 1 goes out
         // now, behind the fill, and is waited for inside the loop.
-#if ZRC4_LINE0_ASM
-        if constexpr (PF)
-            asm volatile("s_waitcnt vmcnt(16)" : "+{v[40:71]}"(P) :: "memory");   // younger: the 16 image stores
-        else
-            asm volatile("" : "+{v[40:71]}"(P));
-#else
         asm volatile("" : "+{v[40:71]}"(P));
-#endif
         p_async = false;
         if (ls.wmax > 2u) issue_line1_asm(Q, ls, sk);
         if (k_t == 1u) stream_stamp(sink, 11);       // ZRC4_TIMING: boundary 0, tables read / met
         if constexpr (GR) {
             if (more) {
-                const BucketView bv = PG ? bucket_read_pair(grp, grp + kGrPairCnt + 256u * ((bk - 1u) & 1u), wn, err)
-                                         : bucket_read(gr, wn, err);
+                const BucketView bv = bucket_read_pair(grp, grp + kGrPairCnt + 256u * ((bk - 1u) & 1u), wn, err);
                 if (k_t == 1u) stream_stamp(sink, 10);   // ZRC4_TIMING: boundary 0, next bucket's view read
                 gn = bv.g;
                 nok = bv.ok;
-                // raw entries of the bucket after next (PG: two after next)
-                const uint32_t ea = (wn + (PG ? 2u : 1u) * gridDim.x) * kGroup + j;
+                // raw entries of the bucket two after next
+                const uint32_t ea = (wn + 2u * gridDim.x) * kGroup + j;
                 const uint32_t eq = ea < n ? ea : n - 1u;
-                // the claim: wave 0 (PG: the first wave of each pair) swaps
-#ifndef ZRC4_GR_NOSWAP_AB
-#define ZRC4_GR_NOSWAP_AB 0      // timing-only: the claim word read, never swapped (claims off)
-#endif
-                const bool preclaimed = PG && pre && bk < ZRC4_GR_PRECLAIM_MAX;   // (bk: wn's index)
+                // the claim: the first wave of each pair swaps
+                const bool preclaimed = pre && bk < ZRC4_GR_PRECLAIM_MAX;   // (bk: wn's index)
                 const uint32_t dc = __builtin_amdgcn_readfirstlane(
-                    !ZRC4_GR_NOSWAP_AB && !preclaimed && nok && (j & (PG ? 127u : 255u)) < 64u ? 1u : 0u);
+                    !preclaimed && nok && (j & 127u) < 64u ? 1u : 0u);
                 prefetch_bucket(P, Q, ilo, ihi, cold, rlen, roff, rxy, qid, qlen,
-                                reinterpret_cast<const uint32_t *>(cl.word + (size_t)gn * kClaimParts + (PG ? pr : 0u)) + 1,
+                                reinterpret_cast<const uint32_t *>(cl.word + (size_t)gn * kClaimParts + pr) + 1,
                                 cl.epoch,
                                 dc, bv.valid ? len + bv.ent : cl.zero,
                                 bv.valid ? off + bv.ent : reinterpret_cast<const uint64_t *>(cl.zero),
@@ -2709,15 +2452,13 @@ crypt_stream_kernel(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy,
         }
 
         // ---- keystream over this group's messages
-#if ZRC4_PRIO == 1
         {
-            const uint32_t hw = hw_id();                 // ZRC4_PRIO (above the line loop)
+            const uint32_t hw = hw_id();                 // priority by wave slot parity (above the line loop)
             if (((hw ^ k_t) & 1u) != 0u)
                 __builtin_amdgcn_s_setprio(2);
             else
                 __builtin_amdgcn_s_setprio(1);
         }
-#endif
         stream_stamp(sink, 1u + 2u * k_t);
         {
             Rc4Lane st;
@@ -2761,20 +2502,13 @@ crypt_stream_kernel(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy,
             line_setup(ls, payload + nxt.off, nxt.len);
             if (k_t == 1u) stream_stamp(sink, 12);   // ZRC4_TIMING: boundary 0, next entries in
             if (!p_async) {
-#if ZRC4_LINE0_ASM
-                if constexpr (PF) issue_line0_asm(P, ls, sk);
-                else preload_line0(P, ls, sk);
-#else
                 preload_line0(P, ls, sk);
-#endif
             }
         }
 
         // ---- this group's state back to HBM
         if (whole) {
-#if ZRC4_PAIR
-            if constexpr (PF && (!GR || PG)) pair_meet(pctr, pgen); else
-#endif
+            if constexpr (PF) pair_meet(pctr, pgen); else
             __syncthreads();
             lds_to_image_asm(arena + (size_t)g * kGroupBytes, j);
             if (k_t == 1u) stream_stamp(sink, 13);   // ZRC4_TIMING: boundary 0, image out
@@ -2787,9 +2521,7 @@ crypt_stream_kernel(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy,
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
         if (!more) break;
-#if ZRC4_PAIR
-        if constexpr (PF && (!GR || PG)) pair_meet(pctr, pgen); else
-#endif
+        if constexpr (PF) pair_meet(pctr, pgen); else
         __syncthreads();      // every wave has read this image out of LDS before the next fill
         cur = nxt;
         w = wn;
@@ -2930,13 +2662,6 @@ __device__ __forceinline__ void ksa32_window_asm(uint32_t &x0, uint32_t &x1, uin
         : "memory");
 }
 
-#ifndef ZRC4_KSA_WIN32
-#define ZRC4_KSA_WIN32 1
-#endif
-#ifndef ZRC4_KSA_EAB
-#define ZRC4_KSA_EAB 0       // timing-only: skip assembling E (outputs wrong)
-#endif
-
 // ksa_kernel's LDS: the 64 KiB S-box image, then 16 KiB of key schedule
 // prefixes (window path: dword w of lane j at kKsaSched + 4 * (w * 256 + j),
 // conflict-free for any per-lane w).  80 KiB: two workgroups per CU.
@@ -3034,7 +2759,7 @@ ksa_kernel(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy,
             for (int k = 0; k < 256; ++k) S[(k << 8) | col] = (uint8_t)k;
     }
 
-    if (winpath && !ZRC4_KSA_EAB) {
+    if (winpath) {
         // X = key || key[0..2] as aligned dwords in the schedule rows, then
         // E dword w = X bytes r .. r+3 with r = 4w mod len (one byte align).
         uint32_t K[12];
@@ -3089,7 +2814,6 @@ ksa_kernel(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy,
             uint32_t x0 = col, x1 = (1u << 8) | col, a0 = S[col];
             uint32_t ya = col | ((sch[0] & 0xFFu) << 8);   // j = 0 + key[0] before step 0
             uint32_t k = 0;                                // 16c mod len
-#if ZRC4_KSA_WIN32
             if (kl <= 32u) {
                 // 32-step chunks: 33 bytes E[k .. k+32], k = 32c mod len <= 31
                 uint32_t d[9];
@@ -3112,7 +2836,6 @@ ksa_kernel(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy,
                     ksa32_window_asm(x0, x1, a0, ya, q);
                 }
             } else
-#endif
             {
             uint32_t d[5];
 #pragma unroll
