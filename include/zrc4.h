@@ -171,6 +171,39 @@ int zrc4_crypt_grouped_declared(zrc4_ctx *ctx, const uint32_t *ids,
                                 uint32_t n, const struct zrc4_frame_args *frame,
                                 void *stream);
 
+/* Write-only keystream: zrc4_crypt_range / zrc4_crypt_grouped with one
+ * difference: entry i STORES the next len[i] keystream bytes of its slot into
+ * out[off[i] .. off[i]+len[i]) and advances the slot by len[i] bytes.  The
+ * previous contents of `out` are never read (no zeroing by the caller, no
+ * load of the destination: what a keystream reservoir refills its rings
+ * with).  Everything else is the crypt calls': the slot rules, the bucket
+ * contract, the claims and their per-part refusals, n <= 0xFFF00000, no
+ * capture into a replayed HIP graph, disjoint 256-slot groups for concurrent
+ * streams, and the faults latched for zrc4_sync.  bucket_group: NULL, or HOST
+ * memory with zrc4_crypt_grouped_declared's meaning and rules (a group >=
+ * capacity / 256 returns ZRC4_ERR_INVALID_ARG and launches nothing).
+ *   - bytes outside the spans are not written;
+ *   - the span of a skipped entry (ids[i] == ZRC4_IDLE_SLOT, len[i] == 0, or
+ *     an id >= capacity, reported as ZRC4_ERR_SLOT_RANGE) is left untouched;
+ *   - the spans of a bucket refused with ZRC4_ERR_GROUP are unspecified:
+ *     untouched or zero.  Its slots' states are untouched.
+ * `out` is device memory or coherent pinned host memory, at any alignment
+ * (16-byte aligned span starts store whole 16-byte units).  With at most one
+ * group or bucket per CU the kernels store the keystream themselves, in one
+ * launch.  With more (the persistent throughput kernel, which has no
+ * write-only form) the call makes TWO launches on `stream`: a short kernel
+ * that zeroes the span of every entry that is not skipped, then the crypt
+ * launch over the zeroed spans (0 ^ k = k); the destination is then written
+ * twice and read once, by the device only.  There are no _host or _frame
+ * variants.  Device pointers apart from bucket_group; asynchronous. */
+int zrc4_keystream_range(zrc4_ctx *ctx, uint32_t first_slot, uint8_t *out,
+                         const uint64_t *off, const uint32_t *len, uint32_t n,
+                         void *stream);
+int zrc4_keystream_grouped(zrc4_ctx *ctx, const uint32_t *ids,
+                           const uint32_t *bucket_group, uint8_t *out,
+                           const uint64_t *off, const uint32_t *len, uint32_t n,
+                           void *stream);
+
 /* Host-pointer variants: copy to the device (pinned staging), run, copy back,
  * block until done.  payload_bytes bounds the host payload buffer.
  * zrc4_crypt_host checks every id on the host first: an id >= capacity
@@ -196,8 +229,10 @@ int zrc4_encryption(zrc4_ctx *ctx, uint32_t id, uint8_t *data, int length);
 /* Keystream reservoirs (the session engine's low-latency hook path,
  * zsummerx_amd/engine/rc4_hooks_device.cpp).  RC4's keystream does not depend
  * on the data, so a slot's keystream can be generated ahead into a device
- * ring of ring_cap bytes (ring r at ring + r * ring_cap) by zrc4_crypt over
- * ZEROED ring bytes (0 ^ k = k; the slot's state advances as usual).
+ * ring of ring_cap bytes (ring r at ring + r * ring_cap): by
+ * zrc4_keystream_range / zrc4_keystream_grouped (above) whatever the ring
+ * holds, or by zrc4_crypt over ZEROED ring bytes (0 ^ k = k; the slot's state
+ * advances as usual).
  * zrc4_xor_ring then XORs entry i's payload[off[i] .. off[i]+len[i]) with
  * ring rid[i] from position pos[i] on (wrapping mod ring_cap) and zeroes the
  * ring bytes it used.  Requires len[i] <= ring_cap and pos[i] < ring_cap; the
@@ -258,11 +293,12 @@ int zrc4_crypt_grouped_frame(zrc4_ctx *ctx, const uint32_t *ids, uint8_t *payloa
                              const uint64_t *off, const uint32_t *len, uint32_t n,
                              const zrc4_frame_args *frame, void *stream);
 
-/* Wait for `stream`, then report (and clear) any latched device-side fault. */
 /* Keystream reservoir over a context (the C++ mirror's per-call path):
  * per-slot rings of ring_bytes in pinned host memory that the device fills
- * ahead with the slot's keystream (background stream, one grouped launch for
- * every slot used since the last refill).  zrc4_ks_crypt XORs host spans with
+ * ahead with the slot's keystream (background stream, one write-only grouped
+ * launch -- zrc4_keystream_grouped's path -- for every slot used since the
+ * last refill; consumed ring bytes keep their keystream until a later refill
+ * overwrites them).  zrc4_ks_crypt XORs host spans with
  * committed ring bytes on the host and crypts only what the rings do not
  * cover on the device, so steady-state calls make no GPU round trip; output
  * bytes are exactly RC4Encryption::encryption's.  Once a slot is used through
@@ -289,6 +325,7 @@ int zrc4_ks_make_sbox(zrc4_ks *ks, uint32_t id, const uint8_t *key,
 int zrc4_ks_copy(zrc4_ks *dst_ks, uint32_t dst, zrc4_ks *src_ks, uint32_t src);
 int zrc4_ks_stats(zrc4_ks *ks, uint64_t out[6]);
 
+/* Wait for `stream`, then report (and clear) any latched device-side fault. */
 int zrc4_sync(zrc4_ctx *ctx, void *stream);
 
 /* Report (and clear) faults latched by kernels that have already completed

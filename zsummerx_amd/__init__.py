@@ -145,6 +145,26 @@ class Context:
                                                     _ptr(length), n, C.byref(fa) if fa is not None else None,
                                                     _stream(stream)), "zrc4_crypt_grouped_declared")
 
+    def keystream_range(self, first_slot: int, out, off, length, n=None, stream=None) -> None:
+        """zrc4_keystream_range: crypt_range's slot rules, but entry i STORES its
+        slot's next length[i] keystream bytes into out (never read)."""
+        n = int(length.numel() if n is None else n)
+        check(self._lib.zrc4_keystream_range(self._h, int(first_slot), _ptr(out), _ptr(off), _ptr(length), n,
+                                             _stream(stream)), "zrc4_keystream_range")
+
+    def keystream_grouped(self, out, off, length, ids, bucket_group=None, n=None, stream=None) -> None:
+        """zrc4_keystream_grouped: crypt_grouped's buckets (declared from the
+        host when bucket_group is given: ceil(n/256) ints, IDLE_SLOT for an
+        idle bucket), storing keystream into out (never read)."""
+        n = int(length.numel() if n is None else n)
+        bg = None
+        if bucket_group is not None:
+            bg = np.ascontiguousarray(bucket_group, dtype=np.uint32)
+            if bg.size < -(-n // GROUP_SLOTS):
+                raise ValueError("bucket_group needs one entry per 256-entry bucket")
+        check(self._lib.zrc4_keystream_grouped(self._h, _ptr(ids), _ptr(bg), _ptr(out), _ptr(off), _ptr(length), n,
+                                               _stream(stream)), "zrc4_keystream_grouped")
+
     @staticmethod
     def _frame(frame: dict) -> FrameArgs:
         return FrameArgs(_ptr(frame["off"]), _ptr(frame["len"]), int(frame["bound"]), int(frame.get("max_packets", 0)),

@@ -155,6 +155,9 @@ def build_test_tools(force: bool = False, sanitize: bool | str = False) -> Path:
       tools/bin/frame_stress_emu the engine + device hooks over that emulation
       tools/bin/emu_declared_check  the emulation's declared-group refusals
                                  against the GPU's rules
+      tools/bin/emu_keystream_check the emulated write-only keystream calls
+                                 (tests/cpp/emu_zrc4_keystream.cpp) against
+                                 the oracle and the header's rules
     sanitize=True builds only the two emulated binaries, with ASan + UBSan,
     into tools/bin/san/ (scripts/sanitize.sh runs the CPU suites on them);
     sanitize="thread" the same with ThreadSanitizer into tools/bin/tsan/ (the
@@ -166,6 +169,8 @@ def build_test_tools(force: bool = False, sanitize: bool | str = False) -> Path:
     orc = ROOT / "oracle" / "liboracle.so"
     chk = ROOT / "tests" / "cpp" / "hooks_check.cpp"
     emu = ROOT / "tests" / "cpp" / "emu_zrc4_hip.cpp"
+    emu_ks = ROOT / "tests" / "cpp" / "emu_zrc4_keystream.cpp"    # zrc4_keystream_* over emu's public ABI
+    ks_chk = ROOT / "tests" / "cpp" / "emu_keystream_check.cpp"
     dev = ENGINE / "rc4_hooks_device.cpp"
     common = ["-std=c++17", f"-I{ROOT / 'include'}", f"-I{ROOT / 'oracle'}"]
     emu_flags = ["-D__HIP_PLATFORM_AMD__", f"-I{ROCM / 'include'}"]
@@ -175,15 +180,18 @@ def build_test_tools(force: bool = False, sanitize: bool | str = False) -> Path:
          ["g++", "-O2", *common, "-o", str(out / "hooks_check"), str(chk), *oracle_link,
           f"-L{PKG}", "-lzsx_frame", "-lzrc4", "-lpthread", "-Wl,-rpath,$ORIGIN/../../zsummerx_amd",
           f"-Wl,-rpath,{ROCM / 'lib'}"]),
-        (out / "hooks_check_emu", [chk, orc, emu] + FRAME_DEPS,
+        (out / "hooks_check_emu", [chk, orc, emu, emu_ks] + FRAME_DEPS,
          ["g++", "-O2", *common, *emu_flags, "-o", str(out / "hooks_check_emu"), str(chk), str(dev), str(emu),
-          *oracle_link, "-lpthread"]),
-        (out / "emu_declared_check", [orc, emu, ROOT / "tests" / "cpp" / "emu_declared_check.cpp", ROOT / "include" / "zrc4.h"],
+          str(emu_ks), *oracle_link, "-lpthread"]),
+        (out / "emu_declared_check", [orc, emu, emu_ks, ROOT / "tests" / "cpp" / "emu_declared_check.cpp", ROOT / "include" / "zrc4.h"],
          ["g++", "-O2", *common, *emu_flags, "-o", str(out / "emu_declared_check"),
-          str(ROOT / "tests" / "cpp" / "emu_declared_check.cpp"), str(emu), *oracle_link, "-lpthread"]),
-        (out / "frame_stress_emu", [orc, emu, ROOT / "tools" / "frame_stress.cpp"] + FRAME_DEPS,
+          str(ROOT / "tests" / "cpp" / "emu_declared_check.cpp"), str(emu), str(emu_ks), *oracle_link, "-lpthread"]),
+        (out / "emu_keystream_check", [orc, emu, emu_ks, ks_chk, ROOT / "include" / "zrc4.h"],
+         ["g++", "-O2", *common, *emu_flags, "-o", str(out / "emu_keystream_check"), str(ks_chk), str(emu),
+          str(emu_ks), *oracle_link, "-lpthread"]),
+        (out / "frame_stress_emu", [orc, emu, emu_ks, ROOT / "tools" / "frame_stress.cpp"] + FRAME_DEPS,
          ["g++", "-O2", *common, *emu_flags, "-o", str(out / "frame_stress_emu"), str(ROOT / "tools" / "frame_stress.cpp"),
-          *map(str, FRAME_SOURCES), str(emu), *oracle_link, "-ldl", "-lpthread"]),
+          *map(str, FRAME_SOURCES), str(emu), str(emu_ks), *oracle_link, "-ldl", "-lpthread"]),
     ]
     if sanitize:
         flags = TSAN if sanitize == "thread" else SANITIZE

@@ -110,11 +110,19 @@ constexpr size_t kZeroCopyMax = 256u << 10;   // *_host batches up to this size 
 // it first in decl_check_kernel, which blocks the groups of a disagreeing
 // bucket through the claims.  `decl_trusted`: the groups were computed here
 // from host ids (zrc4_crypt_host), so larger launches skip the check.
+//
+// `ks` (kRange / kGrouped, never with `fr`): write-only keystream
+// (zrc4_keystream_*): every entry's span receives its slot's next len bytes of
+// keystream and is never read.  The window, half- and whole-group kernels have
+// a KS form of their own; the persistent kernel has none, so there the spans
+// are zeroed first by span_fill_kernel on the same stream (0 ^ k = k).
 int launch_crypt(zrc4_ctx *c, int mode, const uint32_t *ids, uint32_t first_slot, uint8_t *payload,
                  const uint64_t *off, const uint32_t *len, uint32_t n, hipStream_t s,
-                 const zrc4::FrameArgs *fr = nullptr, const uint32_t *decl = nullptr, bool decl_trusted = false)
+                 const zrc4::FrameArgs *fr = nullptr, const uint32_t *decl = nullptr, bool decl_trusted = false,
+                 bool ks = false)
 {
     if (n == 0) return ZRC4_OK;
+    if (ks && (fr || mode == zrc4::kIds)) return ZRC4_ERR_INVALID_ARG;
     if (mode == zrc4::kRange && (uint64_t)first_slot + n > c->capacity) return ZRC4_ERR_SLOT_RANGE;
     zrc4::Claim cl{nullptr, 0u, nullptr};
     if (mode == zrc4::kGrouped) {
@@ -143,21 +151,27 @@ int launch_crypt(zrc4_ctx *c, int mode, const uint32_t *ids, uint32_t first_slot
         zrc4::WinGroups dg{};
         if (decl && mode == zrc4::kGrouped)
             for (uint32_t b = 0; b < grid; ++b) dg.g[b] = decl[b];
-#define ZRC4_WIN(MODE_, FRAME_, DECL_)                                                                          \
-    hipLaunchKernelGGL((zrc4::crypt_win_kernel<MODE_, FRAME_, DECL_>), wgrid, wblk, 0, s, c->arena, c->xy, ids, \
-                       first_slot, payload, off, len, n, c->capacity, c->err, c->sink, fa, cl, dg)
-        if (mode == zrc4::kRange && fr)
-            ZRC4_WIN(zrc4::kRange, true, false);
+#define ZRC4_WIN(MODE_, FRAME_, DECL_, KS_)                                                                 \
+    hipLaunchKernelGGL((zrc4::crypt_win_kernel<MODE_, FRAME_, DECL_, KS_>), wgrid, wblk, 0, s, c->arena, c->xy, \
+                       ids, first_slot, payload, off, len, n, c->capacity, c->err, c->sink, fa, cl, dg)
+        if (ks && mode == zrc4::kRange)
+            ZRC4_WIN(zrc4::kRange, false, false, true);
+        else if (ks && decl)
+            ZRC4_WIN(zrc4::kGrouped, false, true, true);
+        else if (ks)
+            ZRC4_WIN(zrc4::kGrouped, false, false, true);
+        else if (mode == zrc4::kRange && fr)
+            ZRC4_WIN(zrc4::kRange, true, false, false);
         else if (mode == zrc4::kRange)
-            ZRC4_WIN(zrc4::kRange, false, false);
+            ZRC4_WIN(zrc4::kRange, false, false, false);
         else if (decl && fr)
-            ZRC4_WIN(zrc4::kGrouped, true, true);
+            ZRC4_WIN(zrc4::kGrouped, true, true, false);
         else if (decl)
-            ZRC4_WIN(zrc4::kGrouped, false, true);
+            ZRC4_WIN(zrc4::kGrouped, false, true, false);
         else if (fr)
-            ZRC4_WIN(zrc4::kGrouped, true, false);
+            ZRC4_WIN(zrc4::kGrouped, true, false, false);
         else
-            ZRC4_WIN(zrc4::kGrouped, false, false);
+            ZRC4_WIN(zrc4::kGrouped, false, false, false);
 #undef ZRC4_WIN
         return hipGetLastError() == hipSuccess ? ZRC4_OK : ZRC4_ERR_LAUNCH;
     }
@@ -168,17 +182,21 @@ int launch_crypt(zrc4_ctx *c, int mode, const uint32_t *ids, uint32_t first_slot
         for (uint32_t b = 0; b < grid; ++b) dg.g[b] = decl[b];
         const zrc4::FrameArgs fa = fr ? *fr : zrc4::FrameArgs{};
         const bool half = 2u * grid <= (uint32_t)c->num_cus;
-#define ZRC4_DECL(FRAME_, HALF_, GRID_, BLK_)                                                                  \
-    hipLaunchKernelGGL((zrc4::crypt_decl_kernel<FRAME_, HALF_>), GRID_, BLK_, 0, s, c->arena, c->xy, ids, payload, \
-                       off, len, n, c->capacity, c->err, c->sink, fa, cl, dg)
-        if (half && fr)
-            ZRC4_DECL(true, true, dim3(2u * grid), dim3(zrc4::kHalfBlock));
+#define ZRC4_DECL(FRAME_, HALF_, KS_, GRID_, BLK_)                                                         \
+    hipLaunchKernelGGL((zrc4::crypt_decl_kernel<FRAME_, HALF_, KS_>), GRID_, BLK_, 0, s, c->arena, c->xy, ids, \
+                       payload, off, len, n, c->capacity, c->err, c->sink, fa, cl, dg)
+        if (half && ks)
+            ZRC4_DECL(false, true, true, dim3(2u * grid), dim3(zrc4::kHalfBlock));
+        else if (ks)
+            ZRC4_DECL(false, false, true, dim3(grid), blk);
+        else if (half && fr)
+            ZRC4_DECL(true, true, false, dim3(2u * grid), dim3(zrc4::kHalfBlock));
         else if (half)
-            ZRC4_DECL(false, true, dim3(2u * grid), dim3(zrc4::kHalfBlock));
+            ZRC4_DECL(false, true, false, dim3(2u * grid), dim3(zrc4::kHalfBlock));
         else if (fr)
-            ZRC4_DECL(true, false, dim3(grid), blk);
+            ZRC4_DECL(true, false, false, dim3(grid), blk);
         else
-            ZRC4_DECL(false, false, dim3(grid), blk);
+            ZRC4_DECL(false, false, false, dim3(grid), blk);
 #undef ZRC4_DECL
         return hipGetLastError() == hipSuccess ? ZRC4_OK : ZRC4_ERR_LAUNCH;
     }
@@ -216,7 +234,13 @@ int launch_crypt(zrc4_ctx *c, int mode, const uint32_t *ids, uint32_t first_slot
         const dim3 hblk(zrc4::kHalfBlock);
         const dim3 hgrid(mode == zrc4::kGrouped ? 2u * grid : (n + zrc4::kGroup / 2 - 1) / (zrc4::kGroup / 2));
         const zrc4::FrameArgs fa = fr ? *fr : zrc4::FrameArgs{};
-        if (mode == zrc4::kRange) {
+        if (ks && mode == zrc4::kRange)
+            hipLaunchKernelGGL((zrc4::crypt_half_kernel<zrc4::kRange, false, true>), hgrid, hblk, 0, s, c->arena,
+                               c->xy, ids, first_slot, payload, off, len, n, c->capacity, c->err, c->sink, fa);
+        else if (ks)
+            hipLaunchKernelGGL((zrc4::crypt_half_kernel<zrc4::kGrouped, false, true>), hgrid, hblk, 0, s, c->arena,
+                               c->xy, ids, first_slot, payload, off, len, n, c->capacity, c->err, c->sink, fa, cl);
+        else if (mode == zrc4::kRange) {
             if (fr)
                 hipLaunchKernelGGL((zrc4::crypt_half_kernel<zrc4::kRange, true>), hgrid, hblk, 0, s, c->arena, c->xy,
                                    ids, first_slot, payload, off, len, n, c->capacity, c->err, c->sink, fa);
@@ -244,7 +268,25 @@ int launch_crypt(zrc4_ctx *c, int mode, const uint32_t *ids, uint32_t first_slot
             return ZRC4_ERR_INVALID_ARG;
         return hipGetLastError() == hipSuccess ? ZRC4_OK : ZRC4_ERR_LAUNCH;
     }
+    if (ks && !stream_kernel) {
+        if (mode == zrc4::kRange)
+            hipLaunchKernelGGL((zrc4::crypt_kernel<zrc4::kRange, false, true>), dim3(grid), blk, 0, s, c->arena, c->xy,
+                               ids, first_slot, payload, off, len, n, c->capacity, c->err, c->sink);
+        else
+            hipLaunchKernelGGL((zrc4::crypt_kernel<zrc4::kGrouped, false, true>), dim3(grid), blk, 0, s, c->arena,
+                               c->xy, ids, first_slot, payload, off, len, n, c->capacity, c->err, c->sink,
+                               zrc4::FrameArgs{}, cl);
+        return hipGetLastError() == hipSuccess ? ZRC4_OK : ZRC4_ERR_LAUNCH;
+    }
     if (stream_kernel) {
+        if (ks) {
+            // no write-only form of the persistent kernel: zero the spans it
+            // will crypt (one wave per entry, a few waves per SIMD at most)
+            const uint32_t fgrid = (uint32_t)std::min<uint64_t>(((uint64_t)n + 3u) / 4u, 16u * (uint64_t)c->num_cus);
+            hipLaunchKernelGGL(zrc4::span_fill_kernel, dim3(fgrid), blk, 0, s, mode == zrc4::kGrouped ? ids : nullptr,
+                               payload, off, len, n, c->capacity);
+            if (hipGetLastError() != hipSuccess) return ZRC4_ERR_LAUNCH;
+        }
         // with `fr`, the framing walk runs in the same launch, in each
         // workgroup's tail over the chunks it decrypted (frame_walk_chunks)
         const uint32_t wgs = std::min(grid, 2u * (uint32_t)c->num_cus);
@@ -541,6 +583,34 @@ int zrc4_crypt_grouped_declared(zrc4_ctx *c, const uint32_t *ids, const uint32_t
     if ((rc = set_device(c))) return rc;
     return launch_crypt(c, zrc4::kGrouped, ids, 0, payload, off, len, n, (hipStream_t)stream, frame ? &fr : nullptr,
                         bucket_group);
+}
+
+int zrc4_keystream_range(zrc4_ctx *c, uint32_t first_slot, uint8_t *out, const uint64_t *off, const uint32_t *len,
+                         uint32_t n, void *stream)
+{
+    if (!c) return ZRC4_ERR_INVALID_ARG;
+    if (n && (!out || !off || !len)) return ZRC4_ERR_INVALID_ARG;
+    int rc = set_device(c);
+    if (rc) return rc;
+    return launch_crypt(c, zrc4::kRange, nullptr, first_slot, out, off, len, n, (hipStream_t)stream, nullptr, nullptr,
+                        false, true);
+}
+
+int zrc4_keystream_grouped(zrc4_ctx *c, const uint32_t *ids, const uint32_t *bucket_group, uint8_t *out,
+                           const uint64_t *off, const uint32_t *len, uint32_t n, void *stream)
+{
+    if (!c) return ZRC4_ERR_INVALID_ARG;
+    if (n && (!ids || !out || !off || !len)) return ZRC4_ERR_INVALID_ARG;
+    if (bucket_group) {
+        const uint32_t nb = (uint32_t)(((uint64_t)n + zrc4::kGroup - 1) / zrc4::kGroup);
+        const uint32_t groups = c->capacity / zrc4::kGroup;
+        for (uint32_t b = 0; b < nb; ++b)
+            if (bucket_group[b] >= groups && bucket_group[b] != ZRC4_IDLE_SLOT) return ZRC4_ERR_INVALID_ARG;
+    }
+    int rc = set_device(c);
+    if (rc) return rc;
+    return launch_crypt(c, zrc4::kGrouped, ids, 0, out, off, len, n, (hipStream_t)stream, nullptr, bucket_group, false,
+                        true);
 }
 
 int zrc4_xor_ring(zrc4_ctx *c, uint8_t *ring, uint32_t ring_cap, const uint32_t *rid,

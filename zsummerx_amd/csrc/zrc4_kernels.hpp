@@ -422,17 +422,24 @@ __device__ __forceinline__ uint32_t head_bytes(const uint8_t *msg, uint32_t len)
 #define ZL_XOR(R, SEL, K)                                                                        \
     "v_xor_b32_sdwa " #R ", " #R ", %[" #K "] dst_sel:" #SEL                                     \
     " dst_unused:UNUSED_PRESERVE src0_sel:" #SEL " src1_sel:BYTE_0\n\t"
-#define ZL_W0(D)                                                                                 \
-    ZRC4_E ZRC4_O ZL_XOR(D, BYTE_0, k0) ZRC4_E ZL_XOR(D, BYTE_1, k1)                            \
-    ZRC4_O ZL_XOR(D, BYTE_2, k0)
-#define ZL_W(DP, D)                                                                              \
-    ZRC4_E ZL_XOR(DP, BYTE_3, k1) ZRC4_O ZL_XOR(D, BYTE_0, k0)                                  \
-    ZRC4_E ZL_XOR(D, BYTE_1, k1) ZRC4_O ZL_XOR(D, BYTE_2, k0)
-#define ZL_BLOCK(d0, d1, d2, d3, d4, d5, d6, d7, d8, d9, d10, d11, d12, d13, d14, d15)            \
-    ZL_W0(d0) ZL_W(d0, d1) ZL_W(d1, d2) ZL_W(d2, d3) ZL_W(d3, d4) ZL_W(d4, d5)                  \
-    ZL_W(d5, d6) ZL_W(d6, d7) ZL_W(d7, d8) ZL_W(d8, d9) ZL_W(d9, d10) ZL_W(d10, d11)            \
-    ZL_W(d11, d12) ZL_W(d12, d13) ZL_W(d13, d14) ZL_W(d14, d15)                                 \
-    "s_waitcnt lgkmcnt(0)\n\t" ZL_XOR(d15, BYTE_3, k1)
+// Write-only form (KS, zrc4_keystream_*): the keystream byte replaces its byte
+// lane, so a block's registers need no payload and nothing is loaded.
+#define ZL_MOV(R, SEL, K)                                                                        \
+    "v_mov_b32_sdwa " #R ", %[" #K "] dst_sel:" #SEL                                             \
+    " dst_unused:UNUSED_PRESERVE src0_sel:BYTE_0\n\t"
+#define ZL_W0_(X, D)                                                                             \
+    ZRC4_E ZRC4_O X(D, BYTE_0, k0) ZRC4_E X(D, BYTE_1, k1)                                      \
+    ZRC4_O X(D, BYTE_2, k0)
+#define ZL_W_(X, DP, D)                                                                          \
+    ZRC4_E X(DP, BYTE_3, k1) ZRC4_O X(D, BYTE_0, k0)                                            \
+    ZRC4_E X(D, BYTE_1, k1) ZRC4_O X(D, BYTE_2, k0)
+#define ZL_BLOCK_(X, d0, d1, d2, d3, d4, d5, d6, d7, d8, d9, d10, d11, d12, d13, d14, d15)        \
+    ZL_W0_(X, d0) ZL_W_(X, d0, d1) ZL_W_(X, d1, d2) ZL_W_(X, d2, d3) ZL_W_(X, d3, d4)           \
+    ZL_W_(X, d4, d5) ZL_W_(X, d5, d6) ZL_W_(X, d6, d7) ZL_W_(X, d7, d8) ZL_W_(X, d8, d9)        \
+    ZL_W_(X, d9, d10) ZL_W_(X, d10, d11) ZL_W_(X, d11, d12) ZL_W_(X, d12, d13)                  \
+    ZL_W_(X, d13, d14) ZL_W_(X, d14, d15)                                                        \
+    "s_waitcnt lgkmcnt(0)\n\t" X(d15, BYTE_3, k1)
+#define ZL_BLOCK(...) ZL_BLOCK_(ZL_XOR, __VA_ARGS__)
 // payload tuples: A = v40..v55, B = v56..v71
 #define ZL_A0 "v[40:43]"
 #define ZL_A1 "v[44:47]"
@@ -527,6 +534,46 @@ __device__ __forceinline__ void crypt_blocks_asm(Rc4Lane &st, uint4 *&p, uint32_
     p = reinterpret_cast<uint4 *>((uintptr_t)pa);
 }
 
+// The write-only block loop (KS: zrc4_keystream_*): the same ping-pong over
+// the pinned A and B tuples, exec shrinking as lanes run out of blocks, with
+// NO load: a block's 64 keystream bytes replace the bytes of its tuple
+// (ZL_MOV writes all four byte lanes of all 16 registers) and its four stores
+// leave.  The destination is never read.  The only VMEM ops of the loop are
+// the stores, four per block, so the vmcnt(4) ahead of a block says that the
+// stores of the block before the previous one -- the last readers of the
+// tuple about to be rewritten -- have completed (on the first blocks it waits
+// for whatever the caller left in flight, which is harmless).
+#define ZL_KS_HALF(T0, T1, T2, T3, ...)                                                          \
+    ZL_ACTIVE                                                                                    \
+    "s_waitcnt vmcnt(4)\n\t"                                                                     \
+    ZL_BLOCK_(ZL_MOV, __VA_ARGS__)                                                               \
+    ZL_STORE(T0, T1, T2, T3)
+__device__ __forceinline__ void keystream_blocks_asm(Rc4Lane &st, uint4 *&p, uint32_t nblk)
+{
+    u32x4 a0, a1, a2, a3, b0, b1, b2, b3;
+    uint64_t pa = (uint64_t)(uintptr_t)p, save;
+    uint32_t i, b, k0, k1, a1s;
+    asm volatile(
+        "s_mov_b64 %[save], exec\n\t"
+        "s_mov_b32 %[i], 0\n\t"
+        "ZL_LOOP_%=:\n\t"
+        ZL_KS_HALF(ZL_A0, ZL_A1, ZL_A2, ZL_A3, v40, v41, v42, v43, v44, v45, v46, v47, v48, v49, v50, v51, v52,
+                   v53, v54, v55)
+        ZL_KS_HALF(ZL_B0, ZL_B1, ZL_B2, ZL_B3, v56, v57, v58, v59, v60, v61, v62, v63, v64, v65, v66, v67, v68,
+                   v69, v70, v71)
+        "s_branch ZL_LOOP_%=\n\t"
+        "ZL_DONE_%=:\n\t"
+        "s_mov_b64 exec, %[save]\n\t"
+        : [ya] "+v"(st.ya), [ta] "+v"(st.ta), [x0] "+v"(st.x0), [x1] "+v"(st.x1),
+          [a0] "+v"(st.a0), [a1] "=&v"(a1s), [b] "=&v"(b), [k0] "=&v"(k0), [k1] "=&v"(k1),
+          "+{v[88:89]}"(pa), [i] "=&s"(i), [save] "=&s"(save),
+          "=&{v[40:43]}"(a0), "=&{v[44:47]}"(a1), "=&{v[48:51]}"(a2), "=&{v[52:55]}"(a3),
+          "=&{v[56:59]}"(b0), "=&{v[60:63]}"(b1), "=&{v[64:67]}"(b2), "=&{v[68:71]}"(b3)
+        : [nblk] "v"(nblk), [c100] "s"(0x100u)
+        : "memory", "vcc", "scc");
+    p = reinterpret_cast<uint4 *>((uintptr_t)pa);
+}
+
 // Block 0 of a message issued from asm into the pinned A tuples, so hipcc
 // neither counts nor waits for it (crypt_blocks_asm's lead block does).
 __device__ __forceinline__ void issue_block_asm(uint4 (&A)[4], const uint8_t *msg)
@@ -549,28 +596,44 @@ __device__ __forceinline__ void issue_block_asm(uint4 (&A)[4], const uint8_t *ms
 // Crypt one lane's message in place: unaligned head bytes, 64-byte blocks
 // (crypt_blocks_asm), 16-byte chunks, tail bytes.  If `pre` is set, A already
 // holds the first 64-byte block (issued by the caller ahead of the LDS fill).
+// KS (zrc4_keystream_*): the same walk STORES the keystream and reads no byte
+// of msg (A and pre are unused).
+template <bool KS = false>
 __device__ __forceinline__ void crypt_message(uint8_t *S, Rc4Lane &st, uint8_t *msg,
                                               uint32_t len, uint4 (&A)[4], bool pre)
 {
     const uint32_t head = head_bytes(msg, len);
-    for (uint32_t i = 0; i < head; ++i) msg[i] ^= (uint8_t)prga_step(S, st);
+    for (uint32_t i = 0; i < head; ++i) {
+        const uint8_t k = (uint8_t)prga_step(S, st);
+        if constexpr (KS) msg[i] = k;
+        else msg[i] ^= k;
+    }
     msg += head;
     len -= head;
 
     uint4 *p = reinterpret_cast<uint4 *>(msg);
     const uint32_t nblk = len >> 6;
     if (nblk) {
-        if (!pre) issue_block_asm(A, reinterpret_cast<const uint8_t *>(p));
-        crypt_blocks_asm(st, p, nblk, A);
+        if constexpr (KS) {
+            keystream_blocks_asm(st, p, nblk);
+        } else {
+            if (!pre) issue_block_asm(A, reinterpret_cast<const uint8_t *>(p));
+            crypt_blocks_asm(st, p, nblk, A);
+        }
     }
     uint32_t rem = len & 63u;
     while (rem >= 16u) {
-        *p = xor16(S, st, *p);
+        if constexpr (KS) *p = xor16(S, st, make_uint4(0u, 0u, 0u, 0u));
+        else *p = xor16(S, st, *p);
         ++p;
         rem -= 16u;
     }
     uint8_t *t = reinterpret_cast<uint8_t *>(p);
-    for (uint32_t i = 0; i < rem; ++i) t[i] ^= (uint8_t)prga_step(S, st);
+    for (uint32_t i = 0; i < rem; ++i) {
+        const uint8_t k = (uint8_t)prga_step(S, st);
+        if constexpr (KS) t[i] = k;
+        else t[i] ^= k;
+    }
 }
 
 __device__ __forceinline__ uint32_t wave_max(uint32_t v)
@@ -1225,7 +1288,7 @@ struct BucketGroups {
     uint32_t g[kBodyMaxBuckets];
 };
 
-template <int MODE, bool FRAME, bool HALF, bool DECL = false>
+template <int MODE, bool FRAME, bool HALF, bool DECL = false, bool KS = false>
 __device__ __forceinline__ void
 crypt_body(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy,
            const uint32_t *__restrict__ ids, uint32_t first_slot,
@@ -1236,6 +1299,7 @@ crypt_body(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy,
 {
     static_assert(!HALF || MODE != kIds, "half-group workgroups run range and grouped batches");
     static_assert(!DECL || MODE == kGrouped, "declared groups are a grouped-batch form");
+    static_assert(!KS || (!FRAME && MODE != kIds), "write-only keystream: range and grouped batches, never framed");
     __shared__ __attribute__((aligned(16))) uint8_t smem[HALF ? kSmemHalf : kSmemDirect];
     uint8_t *S = smem;
     if (!lds_base_ok(S, err)) return;
@@ -1491,7 +1555,8 @@ crypt_body(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy,
 
     uint8_t *msg = payload + myoff;
     uint4 A[4];
-    const bool pre = active && mylen >= 64u && head_bytes(msg, mylen) == 0u;
+    // (KS stores keystream and loads no payload: there is no block 0 to issue)
+    const bool pre = !KS && active && mylen >= 64u && head_bytes(msg, mylen) == 0u;
     if constexpr (MODE != kIds) {
         // The image was issued before the entry loads still in flight (kRange:
         // len, off and x/y; kGrouped: x/y).  Waited on every path (the
@@ -1533,7 +1598,7 @@ crypt_body(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy,
     if (active) {
         Rc4Lane st;
         lane_init(st, S, col, sxy);
-        crypt_message(S, st, msg, mylen, A, pre);
+        crypt_message<KS>(S, st, msg, mylen, A, pre);
         xy[slot] = lane_xy(st);
     }
     if constexpr (FRAME) {
@@ -1564,7 +1629,7 @@ crypt_body(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy,
 #endif
 }
 
-template <int MODE, bool FRAME = false>
+template <int MODE, bool FRAME = false, bool KS = false>
 __global__ void __launch_bounds__(256, 2)
 crypt_kernel(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy,
              const uint32_t *__restrict__ ids, uint32_t first_slot,
@@ -1573,12 +1638,13 @@ crypt_kernel(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy,
              uint32_t *__restrict__ err, uint8_t *__restrict__ sink, FrameArgs fr = FrameArgs{},
              Claim cl = Claim{})
 {
-    crypt_body<MODE, FRAME, false>(arena, xy, ids, first_slot, payload, off, len, n, capacity, err, sink, fr, cl);
+    crypt_body<MODE, FRAME, false, false, KS>(arena, xy, ids, first_slot, payload, off, len, n, capacity, err, sink, fr,
+                                              cl);
 }
 
 // The grouped forms with declared bucket groups (zrc4_crypt_grouped_declared,
 // 33..256 buckets): the groups in the kernel arguments.
-template <bool FRAME, bool HALF>
+template <bool FRAME, bool HALF, bool KS = false>
 __global__ void __launch_bounds__(256u, HALF ? 1 : 2)
 crypt_decl_kernel(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy,
                   const uint32_t *__restrict__ ids, uint8_t *__restrict__ payload,
@@ -1586,8 +1652,8 @@ crypt_decl_kernel(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy,
                   uint32_t capacity, uint32_t *__restrict__ err, uint8_t *__restrict__ sink, FrameArgs fr,
                   Claim cl, BucketGroups dg)
 {
-    crypt_body<kGrouped, FRAME, HALF, true>(arena, xy, ids, 0u, payload, off, len, n, capacity, err, sink, fr, cl,
-                                            &dg);
+    crypt_body<kGrouped, FRAME, HALF, true, KS>(arena, xy, ids, 0u, payload, off, len, n, capacity, err, sink, fr, cl,
+                                                &dg);
 }
 
 // Half-group workgroups (kRange / kGrouped, few groups): one per CU;
@@ -1595,7 +1661,7 @@ crypt_decl_kernel(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy,
 // which the two waves that work are picked by SIMD (crypt_body).
 constexpr uint32_t kHalfBlock = 256u;
 
-template <int MODE, bool FRAME = false>
+template <int MODE, bool FRAME = false, bool KS = false>
 __global__ void __launch_bounds__(kHalfBlock, 1)
 crypt_half_kernel(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy,
                   const uint32_t *__restrict__ ids, uint32_t first_slot,
@@ -1604,7 +1670,8 @@ crypt_half_kernel(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy,
                   uint32_t *__restrict__ err, uint8_t *__restrict__ sink, FrameArgs fr = FrameArgs{},
                   Claim cl = Claim{})
 {
-    crypt_body<MODE, FRAME, true>(arena, xy, ids, first_slot, payload, off, len, n, capacity, err, sink, fr, cl);
+    crypt_body<MODE, FRAME, true, false, KS>(arena, xy, ids, first_slot, payload, off, len, n, capacity, err, sink, fr,
+                                             cl);
 }
 
 // ---------------------------------------------------------------------------
@@ -2957,6 +3024,34 @@ xor_ring_kernel(uint8_t *__restrict__ ring, uint32_t cap, const uint32_t *__rest
             for (uint32_t j = 0; j < 4; ++j)
                 if (mask & (0xFFu << (8u * j))) bp[j] ^= (uint8_t)(ks >> (8u * j));
         }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// span_fill_kernel: zeroes the span of every entry a crypt launch would run
+// (zrc4_keystream_* with more groups than CUs: the persistent kernel has no
+// write-only form, so the spans are zeroed on the same stream just before it
+// and 0 ^ k = k).  Skipped entries keep their bytes: len 0, and with ids an id
+// >= capacity (ZRC4_IDLE_SLOT included; the crypt launch latches the fault).
+// One wave per entry, grid-stride: bytes up to the first 16-byte boundary,
+// 16-byte units, tail bytes; stores only, nothing outside [off, off + len).
+// ---------------------------------------------------------------------------
+__global__ void __launch_bounds__(256)
+span_fill_kernel(const uint32_t *__restrict__ ids, uint8_t *__restrict__ out, const uint64_t *__restrict__ off,
+                 const uint32_t *__restrict__ len, uint32_t n, uint32_t capacity)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t waves = (uint64_t)gridDim.x * 4u;
+    for (uint64_t e = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6); e < n; e += waves) {
+        const uint32_t L = len[e];
+        if (L == 0u || (ids && ids[e] >= capacity)) continue;
+        uint8_t *p = out + off[e];
+        const uint32_t head = head_bytes(p, L);
+        if (lane < head) p[lane] = 0;
+        const uint32_t body = L - head, units = body >> 4, tail = body & 15u;
+        uint4 *q = reinterpret_cast<uint4 *>(p + head);
+        for (uint32_t u = lane; u < units; u += 64u) q[u] = make_uint4(0u, 0u, 0u, 0u);
+        if (lane < tail) p[head + 16u * units + lane] = 0;
     }
 }
 

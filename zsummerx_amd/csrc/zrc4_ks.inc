@@ -8,17 +8,22 @@
 // AHEAD into a ring of pinned host memory; a call XORs the caller's bytes with
 // committed ring bytes on the host and goes to the device only for what the
 // ring does not cover (a "tail", e.g. a slot's first call after makeSBox).
-// Refills run in the background on their own stream: one grouped crypt over
-// the rings' zeroed bytes (0 ^ k = k) for every slot used since the last
-// refill, at most kDepth queued, committed when their event has completed.
+// Refills run in the background on their own stream: one write-only grouped
+// launch (launch_crypt's ks mode, the path of zrc4_keystream_grouped) that
+// STORES the next keystream bytes of every slot used since the last refill
+// into its ring, whatever the ring held -- it is never read by the device and
+// never zeroed by the host -- at most kDepth queued, committed when their
+// event has completed.
 // The RC4 state never leaves the device and keystream bytes are consumed in
 // order, so every output byte is the reference's.
 //
 // Invariants (per slot: gen = end of committed keystream, use = bytes
 // consumed, pend = end of queued refills; the device state sits at pend):
-//   * the host reads only ring bytes in [use, gen) and zeroes them as it
-//     consumes them; refills write only [pend, pend + chunk), which the ring
-//     size keeps clear of [use, gen);
+//   * the host reads only ring bytes in [use, gen); refills write only
+//     [pend, pend + chunk), which the ring size keeps clear of [use, gen).
+//     The levels alone say which ring bytes hold keystream: consumed bytes
+//     (and a reseeded slot's dropped ones) stay in the ring, stale, until a
+//     later refill overwrites them;
 //   * a tail crypt, a reseed or a state copy first drains every queued refill
 //     (a grouped kernel stores whole 64 KiB group images), then gen = pend =
 //     use for the slots it touches;
@@ -149,7 +154,6 @@ struct zrc4_ks {
             void *p = nullptr;
             const size_t bytes = (size_t)zrc4::kGroup * ring;
             if (hipHostMalloc(&p, bytes, hipHostMallocCoherent) != hipSuccess) return nullptr;
-            memset(p, 0, bytes);
             sl = static_cast<uint8_t *>(p);
             if (!base) base = sl;
         }
@@ -193,8 +197,8 @@ struct zrc4_ks {
         return ZRC4_OK;
     }
 
-    // One grouped crypt over the rings' next free bytes of every hungry slot
-    // (whole chunks only: a launch lasts as long as its longest piece).
+    // One write-only grouped launch into the rings' next free bytes of every
+    // hungry slot (whole chunks only: a launch lasts as long as its longest piece).
     int launchRefill()
     {
         if (!ring || inflight >= kDepth || hungry.empty()) return ZRC4_OK;
@@ -225,7 +229,8 @@ struct zrc4_ks {
         // up-front check above 256 buckets, where they are not used)
         int rc = R.t.build(es) ? (set_device(c) ? ZRC4_ERR_HIP
                                                 : launch_crypt(c, zrc4::kGrouped, R.t.ids.p, 0, base, R.t.off.p,
-                                                               R.t.len.p, R.t.n, sB, nullptr, R.t.groups.data(), true))
+                                                               R.t.len.p, R.t.n, sB, nullptr, R.t.groups.data(), true,
+                                                               true))
                                : ZRC4_ERR_OUT_OF_MEMORY;
         if (rc != ZRC4_OK) {                      // nothing queued: the levels go back
             for (const KsEntry &e : es) lv[e.slot].pend -= e.len;
@@ -260,11 +265,8 @@ struct zrc4_ks {
         return ZRC4_OK;
     }
 
-    void resetRing(uint32_t s)
-    {
-        if (ring && slab[s / zrc4::kGroup]) memset(ringOf(s), 0, ring);
-        lv[s] = KsLevel{};
-    }
+    // (the levels guard the ring bytes: what the ring still holds is never read)
+    void resetRing(uint32_t s) { lv[s] = KsLevel{}; }
 };
 
 extern "C" {
@@ -372,7 +374,6 @@ int zrc4_ks_crypt(zrc4_ks *k, const uint32_t *ids, uint8_t *const *data, const u
                 const uint32_t m = std::min(have - done, k->ring - at);
                 uint8_t *d = data[i] + done, *q = r + at;
                 for (uint32_t b = 0; b < m; ++b) d[b] ^= q[b];
-                memset(q, 0, m);
                 done += m;
             }
             L.use += have;

@@ -27,7 +27,8 @@
 // (ds_max of (window tag << 8) | (255 - l): the read-back names the lowest lane
 // whose j hit that byte this window -> the duplicate-j rule and the keystream
 // rule), and a keystream ring of kWinRing bytes.  Payload is XORed from the
-// ring per chunk of kWinRing bytes, loads issued a chunk ahead.
+// ring per chunk of kWinRing bytes, loads issued a chunk ahead (the write-only
+// KS form stores the ring to the span instead and loads nothing).
 //
 // Arena access: the 4 streams of a workgroup are the 4 slots whose S-box
 // bytes share one dword of every image row (col bits 0-1 = lane >> 5,
@@ -228,13 +229,20 @@ struct WinGroups {
 //             stream's bytes are decrypted; grouped entries that decrypt
 //             nothing (idle ids, length 0, idle buckets) by lane q of the
 //             bucket's workgroup q (entries q + 64r), on the raw bytes.
-template <int MODE, bool FRAME, bool DECL = false>
+//   KS:       write-only keystream (zrc4_keystream_*): no payload prefetch at
+//             all, and the XOR pass is a STORE of the LDS keystream ring to
+//             the span (16-byte units where the span start is 16-byte
+//             aligned, bytes otherwise; never a read-modify-write).  The
+//             grouped claim's ordering is unchanged: nothing is stored
+//             before claim_wait.  Never combined with FRAME.
+template <int MODE, bool FRAME, bool DECL = false, bool KS = false>
 __global__ void __launch_bounds__(64)
 crypt_win_kernel(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy, const uint32_t *__restrict__ ids,
                  uint32_t first_slot, uint8_t *__restrict__ payload, const uint64_t *__restrict__ off,
                  const uint32_t *__restrict__ len, uint32_t n, uint32_t capacity, uint32_t *__restrict__ err,
                  uint8_t *__restrict__ sink, FrameArgs fr, Claim cl, WinGroups dg = WinGroups{})
 {
+    static_assert(!KS || !FRAME, "write-only keystream is never framed");
     Stamps ts;                                   // ZRC4_TIMING builds only (zrc4_kernels.hpp)
     stamp(ts, 0);
     __shared__ __attribute__((aligned(1024))) uint32_t Mk[kWinStreams * 256];
@@ -417,14 +425,18 @@ crypt_win_kernel(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy, const u
     // (units past the message read the lane's sink bytes) so that the
     // compiler's wait for x/y below counts exactly and leaves the claim --
     // issued right after, from asm -- in flight until the first XOR pass.
+    // KS: no prefetch, the span is never read (the compiler's wait for x/y
+    // then precedes the claim, which claim_wait alone waits for).
     uint4 pre[kWinUnits];
+    if constexpr (!KS) {
 #pragma unroll
-    for (uint32_t u = 0; u < kWinUnits; ++u) {
-        const uint32_t pos = 16u * (l + kWinLanes * u);
-        if constexpr (MODE == kGrouped)
-            pre[u] = *reinterpret_cast<const uint4 *>(aligned && pos + 16u <= L ? msg + pos : sink + 16u * lane);
-        else if (aligned && pos + 16u <= L)
-            pre[u] = *reinterpret_cast<const uint4 *>(msg + pos);
+        for (uint32_t u = 0; u < kWinUnits; ++u) {
+            const uint32_t pos = 16u * (l + kWinLanes * u);
+            if constexpr (MODE == kGrouped)
+                pre[u] = *reinterpret_cast<const uint4 *>(aligned && pos + 16u <= L ? msg + pos : sink + 16u * lane);
+            else if (aligned && pos + 16u <= L)
+                pre[u] = *reinterpret_cast<const uint4 *>(msg + pos);
+        }
     }
     if constexpr (MODE == kGrouped) cold = claim_part_async(cl, gclaim, q, wg);
 
@@ -466,6 +478,21 @@ crypt_win_kernel(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy, const u
         // XOR pass of [c0, c1): whole 16-byte units from the prefetch, bytes
         // otherwise (streams already past their end skip it: c1 - c0 would wrap)
         if (c0 >= L) {
+        } else if constexpr (KS) {
+            // store pass: the ring's bytes of [c0, c1) as they are
+            if (aligned) {
+#pragma unroll
+                for (uint32_t u = 0; u < kWinUnits; ++u) {
+                    const uint32_t pos = c0 + 16u * (l + kWinLanes * u);
+                    if (pos + 16u <= c1)
+                        *reinterpret_cast<uint4 *>(msg + pos) =
+                            *reinterpret_cast<const uint4 *>(R + (pos & (kWinRing - 1u)));
+                }
+                const uint32_t tpos = c0 + ((c1 - c0) & ~15u) + l;                  // ragged tail: < 16 bytes
+                if (tpos < c1) msg[tpos] = R[tpos & (kWinRing - 1u)];
+            } else {
+                for (uint32_t pos = c0 + l; pos < c1; pos += kWinLanes) msg[pos] = R[pos & (kWinRing - 1u)];
+            }
         } else if (aligned) {
 #pragma unroll
             for (uint32_t u = 0; u < kWinUnits; ++u) {
@@ -483,11 +510,13 @@ crypt_win_kernel(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy, const u
             for (uint32_t pos = c0 + l; pos < c1; pos += kWinLanes) msg[pos] ^= R[pos & (kWinRing - 1u)];
         }
         // prefetch of the next chunk
-        const uint32_t n0 = c0 + kWinRing;
+        if constexpr (!KS) {
+            const uint32_t n0 = c0 + kWinRing;
 #pragma unroll
-        for (uint32_t u = 0; u < kWinUnits; ++u) {
-            const uint32_t pos = n0 + 16u * (l + kWinLanes * u);
-            if (aligned && pos + 16u <= L) pre[u] = *reinterpret_cast<const uint4 *>(msg + pos);
+            for (uint32_t u = 0; u < kWinUnits; ++u) {
+                const uint32_t pos = n0 + 16u * (l + kWinLanes * u);
+                if (aligned && pos + 16u <= L) pre[u] = *reinterpret_cast<const uint4 *>(msg + pos);
+            }
         }
     }
 

@@ -9,8 +9,9 @@
 // first pinned allocation and an entry's offset is its address minus the base
 // in two's complement, so slabs anywhere in the address space share one launch.
 //
-// Every launch is a zrc4_crypt_grouped_declared batch (the groups built here
-// are declared with it): entries sorted by slot, one
+// Every crypt launch is a zrc4_crypt_grouped_declared batch and every refill a
+// zrc4_keystream_grouped one (the groups built here are declared with both):
+// entries sorted by slot, one
 // 256-entry bucket per 256-slot group touched, so each bucket moves its
 // group's S-boxes as one coalesced 64 KiB image whatever subset of the group
 // the iteration touches (the kIds gather path is never used here).
@@ -22,9 +23,11 @@
 //              byte-serial), so small batches wait on the chain.
 //   reservoir  (default) RC4's keystream does not depend on the data, so each
 //              slot's keystream is generated AHEAD by the GPU -- a background
-//              stream runs zrc4_crypt over the slot's ring bytes (kept zero:
-//              0 ^ k = k) -- into a ring of `ring` bytes in PINNED HOST memory
-//              (written over PCIe by the kernel).  The hook then XORs each
+//              stream runs zrc4_keystream_grouped, which STORES the slot's
+//              next keystream bytes and never reads the ring -- into a ring
+//              of `ring` bytes in PINNED HOST memory (written over PCIe by
+//              the kernel; nothing crosses the link the other way, and the
+//              host never zeroes a ring byte).  The hook then XORs each
 //              span with committed ring bytes on the host: no GPU round trip
 //              on the latency path.  Only a slot whose committed keystream
 //              does not cover its span goes to the GPU synchronously, and only
@@ -34,8 +37,12 @@
 //              wire bytes are the reference's.
 // Ordering rules (streams: A = synchronous work, B = background refill):
 //   * the host reads only ring bytes of COMMITTED refills (their event has
-//     completed), and zeroes them as it consumes them; a refill writes only
-//     ring bytes past the committed end -- the two never touch the same bytes;
+//     completed) that it has not consumed yet; a refill writes only ring
+//     bytes past the committed end -- the two never touch the same bytes.
+//     The levels (Level) alone say which ring bytes hold keystream: consumed
+//     bytes, a reseeded slot's dropped ones and a fresh slab's contents stay
+//     as they are until a refill overwrites them, and are never read
+//     ($ZSX_RING_POISON=1 fills fresh slabs with 0xA5 to show it);
 //   * kernels that touch slot state (ksa, tail crypt, refill) never run on A
 //     and B at once: a grouped kernel stores its whole group image, so A
 //     waits for every queued refill on B before a seed or a tail crypt;
@@ -145,6 +152,14 @@ int launchGrouped(zrc4_ctx *ctx, const Table &t, uint8_t *base, const zrc4_frame
               : zrc4_crypt_grouped(ctx, t.ids.p, base, t.off.p, t.len.p, t.n, s);
 }
 
+// A refill over table t: the write-only launch (every span receives its
+// slot's next keystream bytes, whatever it held), groups declared as above.
+int launchKeystream(zrc4_ctx *ctx, const Table &t, uint8_t *base, hipStream_t s)
+{
+    return zrc4_keystream_grouped(ctx, t.ids.p, t.groups.size() <= 256u ? t.groups.data() : nullptr, base, t.off.p,
+                                  t.len.p, t.n, s);
+}
+
 struct Entry {
     uint32_t slot;
     uint32_t len;
@@ -213,8 +228,8 @@ struct Refill {
     std::vector<std::pair<uint32_t, uint64_t>> ends;
 };
 
-// dst ^= src for n bytes, then src = 0 (word-wise where possible).
-void xorAndClear(uint8_t *__restrict dst, uint8_t *__restrict src, size_t n)
+// dst ^= src for n bytes (word-wise where possible).
+void xorBytes(uint8_t *__restrict dst, const uint8_t *__restrict src, size_t n)
 {
     size_t i = 0;
     for (; i + 8 <= n; i += 8) {
@@ -225,14 +240,13 @@ void xorAndClear(uint8_t *__restrict dst, uint8_t *__restrict src, size_t n)
         std::memcpy(dst + i, &a, 8);
     }
     for (; i < n; ++i) dst[i] ^= src[i];
-    std::memset(src, 0, n);
 }
 
 // One piece of a reservoir call's host work: span bytes ^= committed ring
-// bytes, ring bytes = 0.
+// bytes.
 struct XorJob {
     uint8_t *dst;
-    uint8_t *src;
+    const uint8_t *src;
     uint32_t n;
 };
 
@@ -272,7 +286,7 @@ public:
     void run(const std::vector<XorJob> &jobs, size_t bytes)
     {
         if (!workers_ || bytes < minBytes_ || jobs.size() < 2) {
-            for (const XorJob &j : jobs) xorAndClear(j.dst, j.src, j.n);
+            for (const XorJob &j : jobs) xorBytes(j.dst, j.src, j.n);
             return;
         }
         // contiguous job ranges of about equal bytes, one per thread
@@ -299,7 +313,7 @@ private:
     void work(unsigned part)
     {
         const std::vector<XorJob> &jobs = *jobs_;
-        for (size_t i = bounds_[part]; i < bounds_[part + 1]; ++i) xorAndClear(jobs[i].dst, jobs[i].src, jobs[i].n);
+        for (size_t i = bounds_[part]; i < bounds_[part + 1]; ++i) xorBytes(jobs[i].dst, jobs[i].src, jobs[i].n);
     }
     void loop(unsigned part)
     {
@@ -459,9 +473,10 @@ public:
                       "{\"ring_bytes\": %llu, \"tail_bytes\": %llu, \"tail_launches\": %llu, "
                       "\"refill_bytes\": %llu, \"refill_launches\": %llu, \"refill_waits\": %llu, "
                       "\"ring_cap\": %u, \"refill_chunk\": %u, \"device_framed\": %llu, \"xor_threads\": %u, "
-                      "\"direct_calls\": %llu, \"direct_bytes\": %llu}",
+                      "\"direct_calls\": %llu, \"direct_bytes\": %llu, \"keystream_launches\": %llu}",
                       ringBytes_, tailBytes_, tailLaunches_, refillBytes_, refillLaunches_, refillWaits_, ringCap_,
-                      refillChunk_, framed_, xor_.threads(), directCalls_, (unsigned long long)directBytes_);
+                      refillChunk_, framed_, xor_.threads(), directCalls_, (unsigned long long)directBytes_,
+                      keystreamLaunches_);
         return b;
     }
 
@@ -473,7 +488,9 @@ private:
     }
 
     // The ring of slot s: pinned host memory, one slab of 256 rings per group,
-    // allocated on first use and zeroed (the zero invariant of the refills).
+    // allocated on first use and left as it comes (refills store into it and
+    // the levels guard what is read; $ZSX_RING_POISON=1, a test knob, fills it
+    // with 0xA5 so that a byte read outside the levels cannot pass for zero).
     uint8_t *ringOf(uint32_t s)
     {
         uint8_t *&slab = ringSlab_[s / ZRC4_GROUP_SLOTS];
@@ -481,7 +498,7 @@ private:
             const size_t bytes = (size_t)ZRC4_GROUP_SLOTS * ringCap_;
             void *p = nullptr;
             if (hipHostMalloc(&p, bytes, hostAllocFlags()) != hipSuccess) throw std::bad_alloc();
-            std::memset(p, 0, bytes);
+            if (ringPoison_) std::memset(p, 0xA5, bytes);
             slab = static_cast<uint8_t *>(p);
         }
         return slab + (size_t)(s % ZRC4_GROUP_SLOTS) * ringCap_;
@@ -631,7 +648,7 @@ private:
         hungry_.swap(keep);
         if (rs_.empty()) return ZRC4_OK;
         buildGrouped(R.t, rs_);
-        int rc = launchGrouped(ctx_, R.t, base_, nullptr, sB_);
+        int rc = launchKeystream(ctx_, R.t, base_, sB_);
         if (rc != ZRC4_OK) {
             // nothing queued: the levels go back (pend > gen with no refill in
             // flight would make cryptReservoir wait for bytes that never come)
@@ -640,6 +657,7 @@ private:
             return rc;
         }
         ++refillLaunches_;
+        ++keystreamLaunches_;
         if (hipEventRecord(R.ev, sB_) != hipSuccess) {
             // the refill is queued but cannot be tracked: wait for stream B
             // and commit its bytes now
@@ -703,8 +721,8 @@ private:
     int drainRefills() { return pollRefills(true); }
 
     // Queued makeSBox calls: one zrc4_ksa ahead of the hook work on A.  In
-    // reservoir mode a reseeded slot's unconsumed keystream is dropped (its
-    // ring bytes zeroed on the host) and its counters restart.
+    // reservoir mode a reseeded slot's unconsumed keystream is dropped: its
+    // counters restart, which is what keeps the stale ring bytes from being read.
     int flushSeeds()
     {
         const uint32_t m = (uint32_t)seedIds_.size();
@@ -712,19 +730,7 @@ private:
         int rc;
         if (ringCap_) {
             if ((rc = drainRefills()) != ZRC4_OK) return rc;
-            for (uint32_t s : seedIds_) {
-                Level &L = level_[s];
-                if (L.gen > L.use) {
-                    uint8_t *r = ringOf(s);
-                    for (uint64_t p = L.use; p < L.gen;) {
-                        const uint32_t at = (uint32_t)(p % ringCap_);
-                        const uint32_t k = (uint32_t)std::min<uint64_t>(L.gen - p, ringCap_ - at);
-                        std::memset(r + at, 0, k);
-                        p += k;
-                    }
-                }
-                L = Level();
-            }
+            for (uint32_t s : seedIds_) level_[s] = Level();
         } else if ((rc = zrc4_sync(ctx_, sA_)) != ZRC4_OK) {
             return rc;
         }
@@ -784,6 +790,7 @@ private:
     unsigned long long directCalls_ = 0;
     const bool debugNoRefill_ = std::getenv("ZSX_RESERVOIR_NO_REFILL") != nullptr;   // test knobs
     const bool debugSyncRefill_ = std::getenv("ZSX_RESERVOIR_SYNC_REFILL") != nullptr;
+    const bool ringPoison_ = std::getenv("ZSX_RING_POISON") != nullptr && std::atoi(std::getenv("ZSX_RING_POISON")) != 0;
 
     zrc4_ctx *ctx_ = nullptr;
     hipStream_t sA_ = nullptr, sB_ = nullptr;
@@ -810,7 +817,7 @@ private:
     std::vector<uint64_t> seedOff_;
     std::vector<uint8_t> keyBytes_;
     unsigned long long ringBytes_ = 0, tailBytes_ = 0, tailLaunches_ = 0, refillBytes_ = 0, refillLaunches_ = 0,
-                       refillWaits_ = 0, framed_ = 0;
+                       refillWaits_ = 0, framed_ = 0, keystreamLaunches_ = 0;
 };
 
 }  // namespace
