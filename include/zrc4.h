@@ -204,6 +204,59 @@ int zrc4_keystream_grouped(zrc4_ctx *ctx, const uint32_t *ids,
                            const uint64_t *off, const uint32_t *len, uint32_t n,
                            void *stream);
 
+/* Out-of-place crypt with shared sources (broadcast encrypt): zrc4_crypt_range
+ * / zrc4_crypt_grouped with one difference: entry i reads a SOURCE span and
+ * writes a DESTINATION span.  It stores src[src_off[i]+k] ^ keystream_i[k]
+ * into dst[dst_off[i]+k] for k < len[i] and advances its slot by len[i] bytes.
+ * One message for N sessions is N entries with the same src_off: the
+ * plaintext is read N times (from cache) and never copied.  Everything else is
+ * the crypt calls': the slot rules, the bucket contract, the claims and their
+ * per-part refusals, n <= 0xFFF00000, no capture into a replayed HIP graph,
+ * disjoint 256-slot groups for concurrent streams, and the faults latched for
+ * zrc4_sync.  bucket_group: NULL, or HOST memory with
+ * zrc4_crypt_grouped_declared's meaning and rules (a group >= capacity / 256
+ * returns ZRC4_ERR_INVALID_ARG and launches nothing).
+ *   - `src` is never written;
+ *   - bytes of `dst` outside the spans are never written;
+ *   - a destination span is never read, except that an entry whose source
+ *     and destination are the SAME ADDRESS is exactly the in-place crypt;
+ *   - source spans may overlap each other freely (the same span N times,
+ *     prefixes of one message, anything);
+ *   - a destination span must not overlap another entry's destination span;
+ *   - a destination span must not overlap any source span other than its own
+ *     identical one; partial overlap of an entry's own two spans is undefined;
+ *   - the span of a skipped entry (ids[i] == ZRC4_IDLE_SLOT, len[i] == 0, or
+ *     an id >= capacity, reported as ZRC4_ERR_SLOT_RANGE) is left untouched
+ *     in `dst`;
+ *   - the destination spans of a bucket refused with ZRC4_ERR_GROUP are
+ *     unspecified: untouched, or a plain copy of the source, never partly
+ *     crypted.  Its slots' states are untouched;
+ *   - launches of at most one group or bucket per CU leave a refused bucket's
+ *     spans untouched: the claim is answered before the first store, as in
+ *     the in-place calls.
+ * `src` and `dst` are device memory or coherent pinned host memory, at any
+ * alignment.  An entry whose two addresses are congruent mod 16 moves 16-byte
+ * units wherever the destination's alignment allows (the in-place walk, loads
+ * from the source); any other entry is crypted byte by byte -- correct, and
+ * much slower per entry, most of all into pinned host memory (DESIGN.md §14
+ * has the numbers): keep sources congruent where it matters.  With at most one group or bucket per CU the kernels read
+ * the sources themselves, in one launch.  With more (the persistent
+ * throughput kernel, which has no out-of-place form) the call makes TWO
+ * launches on `stream`: a short kernel that copies the source span of every
+ * entry that is not skipped into its destination span (entries whose two
+ * addresses are identical are left alone), then the in-place crypt launch over
+ * `dst`; the destination is then written twice and read once, by the device
+ * only.  There are no _host, _frame or scattered-ids (zrc4_crypt) variants.
+ * Device pointers apart from bucket_group; asynchronous. */
+int zrc4_crypt_to_range(zrc4_ctx *ctx, uint32_t first_slot,
+                        const uint8_t *src, const uint64_t *src_off,
+                        uint8_t *dst, const uint64_t *dst_off,
+                        const uint32_t *len, uint32_t n, void *stream);
+int zrc4_crypt_to_grouped(zrc4_ctx *ctx, const uint32_t *ids, const uint32_t *bucket_group,
+                          const uint8_t *src, const uint64_t *src_off,
+                          uint8_t *dst, const uint64_t *dst_off,
+                          const uint32_t *len, uint32_t n, void *stream);
+
 /* Host-pointer variants: copy to the device (pinned staging), run, copy back,
  * block until done.  payload_bytes bounds the host payload buffer.
  * zrc4_crypt_host checks every id on the host first: an id >= capacity

@@ -165,6 +165,29 @@ class Context:
         check(self._lib.zrc4_keystream_grouped(self._h, _ptr(ids), _ptr(bg), _ptr(out), _ptr(off), _ptr(length), n,
                                                _stream(stream)), "zrc4_keystream_grouped")
 
+    def crypt_to_range(self, first_slot: int, src, src_off, dst, dst_off, length, n=None, stream=None) -> None:
+        """zrc4_crypt_to_range: crypt_range's slot rules, out of place: entry i
+        reads src + src_off[i] and stores the XOR to dst + dst_off[i] (sources
+        may be shared between entries; src is never written, dst never read)."""
+        n = int(length.numel() if n is None else n)
+        check(self._lib.zrc4_crypt_to_range(self._h, int(first_slot), _ptr(src), _ptr(src_off), _ptr(dst),
+                                            _ptr(dst_off), _ptr(length), n, _stream(stream)), "zrc4_crypt_to_range")
+
+    def crypt_to_grouped(self, src, src_off, dst, dst_off, length, ids, bucket_group=None, n=None,
+                         stream=None) -> None:
+        """zrc4_crypt_to_grouped: crypt_grouped's buckets (declared from the
+        host when bucket_group is given: ceil(n/256) ints, IDLE_SLOT for an
+        idle bucket), out of place as crypt_to_range."""
+        n = int(length.numel() if n is None else n)
+        bg = None
+        if bucket_group is not None:
+            bg = np.ascontiguousarray(bucket_group, dtype=np.uint32)
+            if bg.size < -(-n // GROUP_SLOTS):
+                raise ValueError("bucket_group needs one entry per 256-entry bucket")
+        check(self._lib.zrc4_crypt_to_grouped(self._h, _ptr(ids), _ptr(bg), _ptr(src), _ptr(src_off), _ptr(dst),
+                                              _ptr(dst_off), _ptr(length), n, _stream(stream)),
+              "zrc4_crypt_to_grouped")
+
     @staticmethod
     def _frame(frame: dict) -> FrameArgs:
         return FrameArgs(_ptr(frame["off"]), _ptr(frame["len"]), int(frame["bound"]), int(frame.get("max_packets", 0)),

@@ -111,18 +111,29 @@ constexpr size_t kZeroCopyMax = 256u << 10;   // *_host batches up to this size 
 // bucket through the claims.  `decl_trusted`: the groups were computed here
 // from host ids (zrc4_crypt_host), so larger launches skip the check.
 //
-// `ks` (kRange / kGrouped, never with `fr`): write-only keystream
+// `io` = zrc4::kIoKs (kRange / kGrouped, never with `fr`): write-only keystream
 // (zrc4_keystream_*): every entry's span receives its slot's next len bytes of
 // keystream and is never read.  The window, half- and whole-group kernels have
 // a KS form of their own; the persistent kernel has none, so there the spans
 // are zeroed first by span_fill_kernel on the same stream (0 ^ k = k).
+//
+// `io` = zrc4::kIoTo with `src` / `src_off` (zrc4_crypt_to_*; the same
+// restrictions as `ks`): entry i reads src + src_off[i] and stores to payload
+// + off[i].  Again the window, half- and whole-group kernels have the form;
+// ahead of the persistent kernel span_copy_kernel copies the sources into the
+// destinations on the same stream, and the in-place launch runs over those.
 int launch_crypt(zrc4_ctx *c, int mode, const uint32_t *ids, uint32_t first_slot, uint8_t *payload,
                  const uint64_t *off, const uint32_t *len, uint32_t n, hipStream_t s,
                  const zrc4::FrameArgs *fr = nullptr, const uint32_t *decl = nullptr, bool decl_trusted = false,
-                 bool ks = false)
+                 int io = zrc4::kIoInPlace, const uint8_t *src = nullptr, const uint64_t *src_off = nullptr)
 {
     if (n == 0) return ZRC4_OK;
-    if (ks && (fr || mode == zrc4::kIds)) return ZRC4_ERR_INVALID_ARG;
+    const bool ks = io == zrc4::kIoKs, to = io == zrc4::kIoTo;
+    if ((ks || to) && (fr || mode == zrc4::kIds)) return ZRC4_ERR_INVALID_ARG;
+    if (to && (!src || !src_off)) return ZRC4_ERR_INVALID_ARG;
+    zrc4::ToArgs ta{};
+    ta.src = src;
+    ta.src_off = src_off;
     if (mode == zrc4::kRange && (uint64_t)first_slot + n > c->capacity) return ZRC4_ERR_SLOT_RANGE;
     zrc4::Claim cl{nullptr, 0u, nullptr};
     if (mode == zrc4::kGrouped) {
@@ -151,28 +162,36 @@ int launch_crypt(zrc4_ctx *c, int mode, const uint32_t *ids, uint32_t first_slot
         zrc4::WinGroups dg{};
         if (decl && mode == zrc4::kGrouped)
             for (uint32_t b = 0; b < grid; ++b) dg.g[b] = decl[b];
-#define ZRC4_WIN(MODE_, FRAME_, DECL_, KS_)                                                                 \
-    hipLaunchKernelGGL((zrc4::crypt_win_kernel<MODE_, FRAME_, DECL_, KS_>), wgrid, wblk, 0, s, c->arena, c->xy, \
-                       ids, first_slot, payload, off, len, n, c->capacity, c->err, c->sink, fa, cl, dg)
-        if (ks && mode == zrc4::kRange)
-            ZRC4_WIN(zrc4::kRange, false, false, true);
+#define ZRC4_WIN_(MODE_, FRAME_, DECL_, IO_, AUX_)                                                             \
+    hipLaunchKernelGGL((zrc4::crypt_win_kernel<MODE_, FRAME_, DECL_, IO_>), wgrid, wblk, 0, s, c->arena, c->xy, \
+                       ids, first_slot, payload, off, len, n, c->capacity, c->err, c->sink, AUX_, cl, dg)
+#define ZRC4_WIN(MODE_, FRAME_, DECL_, IO_) ZRC4_WIN_(MODE_, FRAME_, DECL_, IO_, fa)
+        if (to && mode == zrc4::kRange)
+            ZRC4_WIN_(zrc4::kRange, false, false, zrc4::kIoTo, ta);
+        else if (to && decl)
+            ZRC4_WIN_(zrc4::kGrouped, false, true, zrc4::kIoTo, ta);
+        else if (to)
+            ZRC4_WIN_(zrc4::kGrouped, false, false, zrc4::kIoTo, ta);
+        else if (ks && mode == zrc4::kRange)
+            ZRC4_WIN(zrc4::kRange, false, false, zrc4::kIoKs);
         else if (ks && decl)
-            ZRC4_WIN(zrc4::kGrouped, false, true, true);
+            ZRC4_WIN(zrc4::kGrouped, false, true, zrc4::kIoKs);
         else if (ks)
-            ZRC4_WIN(zrc4::kGrouped, false, false, true);
+            ZRC4_WIN(zrc4::kGrouped, false, false, zrc4::kIoKs);
         else if (mode == zrc4::kRange && fr)
-            ZRC4_WIN(zrc4::kRange, true, false, false);
+            ZRC4_WIN(zrc4::kRange, true, false, zrc4::kIoInPlace);
         else if (mode == zrc4::kRange)
-            ZRC4_WIN(zrc4::kRange, false, false, false);
+            ZRC4_WIN(zrc4::kRange, false, false, zrc4::kIoInPlace);
         else if (decl && fr)
-            ZRC4_WIN(zrc4::kGrouped, true, true, false);
+            ZRC4_WIN(zrc4::kGrouped, true, true, zrc4::kIoInPlace);
         else if (decl)
-            ZRC4_WIN(zrc4::kGrouped, false, true, false);
+            ZRC4_WIN(zrc4::kGrouped, false, true, zrc4::kIoInPlace);
         else if (fr)
-            ZRC4_WIN(zrc4::kGrouped, true, false, false);
+            ZRC4_WIN(zrc4::kGrouped, true, false, zrc4::kIoInPlace);
         else
-            ZRC4_WIN(zrc4::kGrouped, false, false, false);
+            ZRC4_WIN(zrc4::kGrouped, false, false, zrc4::kIoInPlace);
 #undef ZRC4_WIN
+#undef ZRC4_WIN_
         return hipGetLastError() == hipSuccess ? ZRC4_OK : ZRC4_ERR_LAUNCH;
     }
     // Declared groups on the half-group / whole-group kernels (at most 256
@@ -182,22 +201,28 @@ int launch_crypt(zrc4_ctx *c, int mode, const uint32_t *ids, uint32_t first_slot
         for (uint32_t b = 0; b < grid; ++b) dg.g[b] = decl[b];
         const zrc4::FrameArgs fa = fr ? *fr : zrc4::FrameArgs{};
         const bool half = 2u * grid <= (uint32_t)c->num_cus;
-#define ZRC4_DECL(FRAME_, HALF_, KS_, GRID_, BLK_)                                                         \
-    hipLaunchKernelGGL((zrc4::crypt_decl_kernel<FRAME_, HALF_, KS_>), GRID_, BLK_, 0, s, c->arena, c->xy, ids, \
-                       payload, off, len, n, c->capacity, c->err, c->sink, fa, cl, dg)
-        if (half && ks)
-            ZRC4_DECL(false, true, true, dim3(2u * grid), dim3(zrc4::kHalfBlock));
+#define ZRC4_DECL_(FRAME_, HALF_, IO_, GRID_, BLK_, AUX_)                                                   \
+    hipLaunchKernelGGL((zrc4::crypt_decl_kernel<FRAME_, HALF_, IO_>), GRID_, BLK_, 0, s, c->arena, c->xy, ids, \
+                       payload, off, len, n, c->capacity, c->err, c->sink, AUX_, cl, dg)
+#define ZRC4_DECL(FRAME_, HALF_, IO_, GRID_, BLK_) ZRC4_DECL_(FRAME_, HALF_, IO_, GRID_, BLK_, fa)
+        if (half && to)
+            ZRC4_DECL_(false, true, zrc4::kIoTo, dim3(2u * grid), dim3(zrc4::kHalfBlock), ta);
+        else if (to)
+            ZRC4_DECL_(false, false, zrc4::kIoTo, dim3(grid), blk, ta);
+        else if (half && ks)
+            ZRC4_DECL(false, true, zrc4::kIoKs, dim3(2u * grid), dim3(zrc4::kHalfBlock));
         else if (ks)
-            ZRC4_DECL(false, false, true, dim3(grid), blk);
+            ZRC4_DECL(false, false, zrc4::kIoKs, dim3(grid), blk);
         else if (half && fr)
-            ZRC4_DECL(true, true, false, dim3(2u * grid), dim3(zrc4::kHalfBlock));
+            ZRC4_DECL(true, true, zrc4::kIoInPlace, dim3(2u * grid), dim3(zrc4::kHalfBlock));
         else if (half)
-            ZRC4_DECL(false, true, false, dim3(2u * grid), dim3(zrc4::kHalfBlock));
+            ZRC4_DECL(false, true, zrc4::kIoInPlace, dim3(2u * grid), dim3(zrc4::kHalfBlock));
         else if (fr)
-            ZRC4_DECL(true, false, false, dim3(grid), blk);
+            ZRC4_DECL(true, false, zrc4::kIoInPlace, dim3(grid), blk);
         else
-            ZRC4_DECL(false, false, false, dim3(grid), blk);
+            ZRC4_DECL(false, false, zrc4::kIoInPlace, dim3(grid), blk);
 #undef ZRC4_DECL
+#undef ZRC4_DECL_
         return hipGetLastError() == hipSuccess ? ZRC4_OK : ZRC4_ERR_LAUNCH;
     }
     if (decl && mode == zrc4::kGrouped && !decl_trusted) {
@@ -234,12 +259,20 @@ int launch_crypt(zrc4_ctx *c, int mode, const uint32_t *ids, uint32_t first_slot
         const dim3 hblk(zrc4::kHalfBlock);
         const dim3 hgrid(mode == zrc4::kGrouped ? 2u * grid : (n + zrc4::kGroup / 2 - 1) / (zrc4::kGroup / 2));
         const zrc4::FrameArgs fa = fr ? *fr : zrc4::FrameArgs{};
-        if (ks && mode == zrc4::kRange)
-            hipLaunchKernelGGL((zrc4::crypt_half_kernel<zrc4::kRange, false, true>), hgrid, hblk, 0, s, c->arena,
+        if (to && mode == zrc4::kRange)
+            hipLaunchKernelGGL((zrc4::crypt_half_kernel<zrc4::kRange, false, zrc4::kIoTo>), hgrid, hblk, 0, s, c->arena,
+                               c->xy, ids, first_slot, payload, off, len, n, c->capacity, c->err, c->sink, ta);
+        else if (to)
+            hipLaunchKernelGGL((zrc4::crypt_half_kernel<zrc4::kGrouped, false, zrc4::kIoTo>), hgrid, hblk, 0, s,
+                               c->arena, c->xy, ids, first_slot, payload, off, len, n, c->capacity, c->err, c->sink, ta,
+                               cl);
+        else if (ks && mode == zrc4::kRange)
+            hipLaunchKernelGGL((zrc4::crypt_half_kernel<zrc4::kRange, false, zrc4::kIoKs>), hgrid, hblk, 0, s, c->arena,
                                c->xy, ids, first_slot, payload, off, len, n, c->capacity, c->err, c->sink, fa);
         else if (ks)
-            hipLaunchKernelGGL((zrc4::crypt_half_kernel<zrc4::kGrouped, false, true>), hgrid, hblk, 0, s, c->arena,
-                               c->xy, ids, first_slot, payload, off, len, n, c->capacity, c->err, c->sink, fa, cl);
+            hipLaunchKernelGGL((zrc4::crypt_half_kernel<zrc4::kGrouped, false, zrc4::kIoKs>), hgrid, hblk, 0, s,
+                               c->arena, c->xy, ids, first_slot, payload, off, len, n, c->capacity, c->err, c->sink, fa,
+                               cl);
         else if (mode == zrc4::kRange) {
             if (fr)
                 hipLaunchKernelGGL((zrc4::crypt_half_kernel<zrc4::kRange, true>), hgrid, hblk, 0, s, c->arena, c->xy,
@@ -270,12 +303,22 @@ int launch_crypt(zrc4_ctx *c, int mode, const uint32_t *ids, uint32_t first_slot
     }
     if (ks && !stream_kernel) {
         if (mode == zrc4::kRange)
-            hipLaunchKernelGGL((zrc4::crypt_kernel<zrc4::kRange, false, true>), dim3(grid), blk, 0, s, c->arena, c->xy,
-                               ids, first_slot, payload, off, len, n, c->capacity, c->err, c->sink);
+            hipLaunchKernelGGL((zrc4::crypt_kernel<zrc4::kRange, false, zrc4::kIoKs>), dim3(grid), blk, 0, s, c->arena,
+                               c->xy, ids, first_slot, payload, off, len, n, c->capacity, c->err, c->sink);
         else
-            hipLaunchKernelGGL((zrc4::crypt_kernel<zrc4::kGrouped, false, true>), dim3(grid), blk, 0, s, c->arena,
-                               c->xy, ids, first_slot, payload, off, len, n, c->capacity, c->err, c->sink,
+            hipLaunchKernelGGL((zrc4::crypt_kernel<zrc4::kGrouped, false, zrc4::kIoKs>), dim3(grid), blk, 0, s,
+                               c->arena, c->xy, ids, first_slot, payload, off, len, n, c->capacity, c->err, c->sink,
                                zrc4::FrameArgs{}, cl);
+        return hipGetLastError() == hipSuccess ? ZRC4_OK : ZRC4_ERR_LAUNCH;
+    }
+    if (to && !stream_kernel) {
+        if (mode == zrc4::kRange)
+            hipLaunchKernelGGL((zrc4::crypt_kernel<zrc4::kRange, false, zrc4::kIoTo>), dim3(grid), blk, 0, s, c->arena,
+                               c->xy, ids, first_slot, payload, off, len, n, c->capacity, c->err, c->sink, ta);
+        else
+            hipLaunchKernelGGL((zrc4::crypt_kernel<zrc4::kGrouped, false, zrc4::kIoTo>), dim3(grid), blk, 0, s,
+                               c->arena, c->xy, ids, first_slot, payload, off, len, n, c->capacity, c->err, c->sink, ta,
+                               cl);
         return hipGetLastError() == hipSuccess ? ZRC4_OK : ZRC4_ERR_LAUNCH;
     }
     if (stream_kernel) {
@@ -285,6 +328,14 @@ int launch_crypt(zrc4_ctx *c, int mode, const uint32_t *ids, uint32_t first_slot
             const uint32_t fgrid = (uint32_t)std::min<uint64_t>(((uint64_t)n + 3u) / 4u, 16u * (uint64_t)c->num_cus);
             hipLaunchKernelGGL(zrc4::span_fill_kernel, dim3(fgrid), blk, 0, s, mode == zrc4::kGrouped ? ids : nullptr,
                                payload, off, len, n, c->capacity);
+            if (hipGetLastError() != hipSuccess) return ZRC4_ERR_LAUNCH;
+        }
+        if (to) {
+            // no out-of-place form of the persistent kernel: copy the sources
+            // of the entries it will crypt into their destinations
+            const uint32_t fgrid = (uint32_t)std::min<uint64_t>(((uint64_t)n + 3u) / 4u, 16u * (uint64_t)c->num_cus);
+            hipLaunchKernelGGL(zrc4::span_copy_kernel, dim3(fgrid), blk, 0, s, mode == zrc4::kGrouped ? ids : nullptr,
+                               src, src_off, payload, off, len, n, c->capacity);
             if (hipGetLastError() != hipSuccess) return ZRC4_ERR_LAUNCH;
         }
         // with `fr`, the framing walk runs in the same launch, in each
@@ -593,7 +644,7 @@ int zrc4_keystream_range(zrc4_ctx *c, uint32_t first_slot, uint8_t *out, const u
     int rc = set_device(c);
     if (rc) return rc;
     return launch_crypt(c, zrc4::kRange, nullptr, first_slot, out, off, len, n, (hipStream_t)stream, nullptr, nullptr,
-                        false, true);
+                        false, zrc4::kIoKs);
 }
 
 int zrc4_keystream_grouped(zrc4_ctx *c, const uint32_t *ids, const uint32_t *bucket_group, uint8_t *out,
@@ -610,7 +661,36 @@ int zrc4_keystream_grouped(zrc4_ctx *c, const uint32_t *ids, const uint32_t *buc
     int rc = set_device(c);
     if (rc) return rc;
     return launch_crypt(c, zrc4::kGrouped, ids, 0, out, off, len, n, (hipStream_t)stream, nullptr, bucket_group, false,
-                        true);
+                        zrc4::kIoKs);
+}
+
+int zrc4_crypt_to_range(zrc4_ctx *c, uint32_t first_slot, const uint8_t *src, const uint64_t *src_off, uint8_t *dst,
+                        const uint64_t *dst_off, const uint32_t *len, uint32_t n, void *stream)
+{
+    if (!c) return ZRC4_ERR_INVALID_ARG;
+    if (n && (!src || !src_off || !dst || !dst_off || !len)) return ZRC4_ERR_INVALID_ARG;
+    int rc = set_device(c);
+    if (rc) return rc;
+    return launch_crypt(c, zrc4::kRange, nullptr, first_slot, dst, dst_off, len, n, (hipStream_t)stream, nullptr,
+                        nullptr, false, zrc4::kIoTo, src, src_off);
+}
+
+int zrc4_crypt_to_grouped(zrc4_ctx *c, const uint32_t *ids, const uint32_t *bucket_group, const uint8_t *src,
+                          const uint64_t *src_off, uint8_t *dst, const uint64_t *dst_off, const uint32_t *len,
+                          uint32_t n, void *stream)
+{
+    if (!c) return ZRC4_ERR_INVALID_ARG;
+    if (n && (!ids || !src || !src_off || !dst || !dst_off || !len)) return ZRC4_ERR_INVALID_ARG;
+    if (bucket_group) {
+        const uint32_t nb = (uint32_t)(((uint64_t)n + zrc4::kGroup - 1) / zrc4::kGroup);
+        const uint32_t groups = c->capacity / zrc4::kGroup;
+        for (uint32_t b = 0; b < nb; ++b)
+            if (bucket_group[b] >= groups && bucket_group[b] != ZRC4_IDLE_SLOT) return ZRC4_ERR_INVALID_ARG;
+    }
+    int rc = set_device(c);
+    if (rc) return rc;
+    return launch_crypt(c, zrc4::kGrouped, ids, 0, dst, dst_off, len, n, (hipStream_t)stream, nullptr, bucket_group,
+                        false, zrc4::kIoTo, src, src_off);
 }
 
 int zrc4_xor_ring(zrc4_ctx *c, uint8_t *ring, uint32_t ring_cap, const uint32_t *rid,

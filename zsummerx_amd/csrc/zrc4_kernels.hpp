@@ -452,12 +452,16 @@ __device__ __forceinline__ uint32_t head_bytes(const uint8_t *msg, uint32_t len)
 // Next block's four loads into R: from pa + 64, or -- for lanes with no next
 // block -- a harmless re-read of the current block (pa).  pa = v[88:89],
 // pn = v[90:91].
-#define ZL_PREFETCH(R0, R1, R2, R3)                                                              \
+// D: "" (in place: loads and stores share the pointer), or ZL_SRC_DELTA for the
+// out-of-place form, whose loads come from the lane's source = pointer + dl.
+#define ZL_SRC_DELTA "v_lshl_add_u64 v[90:91], v[90:91], 0, %[dl]\n\t"
+#define ZL_PREFETCH_(D, R0, R1, R2, R3)                                                          \
     "s_add_u32 %[i1], %[i], 1\n\t"                                                               \
     "v_cmp_lt_u32_e32 vcc, %[i1], %[nblk]\n\t"                                                   \
     "v_lshl_add_u64 v[90:91], v[88:89], 0, 64\n\t"                                               \
     "v_cndmask_b32_e32 v90, v88, v90, vcc\n\t"                                                   \
     "v_cndmask_b32_e32 v91, v89, v91, vcc\n\t"                                                   \
+    D                                                                                            \
     "global_load_dwordx4 " R0 ", v[90:91], off\n\t"                                              \
     "global_load_dwordx4 " R1 ", v[90:91], off offset:16\n\t"                                    \
     "global_load_dwordx4 " R2 ", v[90:91], off offset:32\n\t"                                    \
@@ -473,21 +477,21 @@ __device__ __forceinline__ uint32_t head_bytes(const uint8_t *msg, uint32_t len)
     "v_cmp_lt_u32_e32 vcc, %[i], %[nblk]\n\t"                                                    \
     "s_and_b64 exec, exec, vcc\n\t"                                                              \
     "s_cbranch_execz ZL_DONE_%=\n\t"
-#define ZL_HALF_A                                                                                \
+#define ZL_HALF_A_(D)                                                                            \
     ZL_ACTIVE                                                                                    \
-    ZL_PREFETCH(ZL_B0, ZL_B1, ZL_B2, ZL_B3)                                                      \
+    ZL_PREFETCH_(D, ZL_B0, ZL_B1, ZL_B2, ZL_B3)                                                  \
     "s_waitcnt vmcnt(8)\n\t"                                                                     \
     ZL_BLOCK(v40, v41, v42, v43, v44, v45, v46, v47, v48, v49, v50, v51, v52, v53, v54, v55)    \
     ZL_STORE(ZL_A0, ZL_A1, ZL_A2, ZL_A3)
-#define ZL_HALF_B                                                                                \
+#define ZL_HALF_B_(D)                                                                            \
     ZL_ACTIVE                                                                                    \
-    ZL_PREFETCH(ZL_A0, ZL_A1, ZL_A2, ZL_A3)                                                      \
+    ZL_PREFETCH_(D, ZL_A0, ZL_A1, ZL_A2, ZL_A3)                                                  \
     "s_waitcnt vmcnt(8)\n\t"                                                                     \
     ZL_BLOCK(v56, v57, v58, v59, v60, v61, v62, v63, v64, v65, v66, v67, v68, v69, v70, v71)    \
     ZL_STORE(ZL_B0, ZL_B1, ZL_B2, ZL_B3)
-#define ZL_FIRST                                                                                 \
+#define ZL_FIRST_(D)                                                                             \
     "s_mov_b32 %[i], 0\n\t"                                                                      \
-    ZL_PREFETCH(ZL_B0, ZL_B1, ZL_B2, ZL_B3)                                                      \
+    ZL_PREFETCH_(D, ZL_B0, ZL_B1, ZL_B2, ZL_B3)                                                  \
     "v_mov_b32 v72, 0\n\tv_mov_b32 v73, 0\n\tv_mov_b32 v74, 0\n\tv_mov_b32 v75, 0\n\t"             \
     "v_mov_b32 v76, 0\n\tv_mov_b32 v77, 0\n\tv_mov_b32 v78, 0\n\tv_mov_b32 v79, 0\n\t"             \
     "v_mov_b32 v80, 0\n\tv_mov_b32 v81, 0\n\tv_mov_b32 v82, 0\n\tv_mov_b32 v83, 0\n\t"             \
@@ -504,6 +508,10 @@ __device__ __forceinline__ uint32_t head_bytes(const uint8_t *msg, uint32_t len)
     "v_xor_b32_e32 v54, v54, v86\n\tv_xor_b32_e32 v55, v55, v87\n\t"                               \
     ZL_STORE(ZL_A0, ZL_A1, ZL_A2, ZL_A3)                                                         \
     "s_branch ZL_MID_%=\n\t"
+
+#define ZL_HALF_A ZL_HALF_A_("")
+#define ZL_HALF_B ZL_HALF_B_("")
+#define ZL_FIRST ZL_FIRST_("")
 
 __device__ __forceinline__ void crypt_blocks_asm(Rc4Lane &st, uint4 *&p, uint32_t nblk,
                                                  const uint4 (&A)[4])
@@ -530,6 +538,42 @@ __device__ __forceinline__ void crypt_blocks_asm(Rc4Lane &st, uint4 *&p, uint32_
           "=&{v[56:59]}"(b0), "=&{v[60:63]}"(b1), "=&{v[64:67]}"(b2), "=&{v[68:71]}"(b3),
           "=&{v[72:75]}"(q0), "=&{v[76:79]}"(q1), "=&{v[80:83]}"(q2), "=&{v[84:87]}"(q3)
         : [nblk] "v"(nblk), [c100] "s"(0x100u)
+        : "memory", "vcc", "scc");
+    p = reinterpret_cast<uint4 *>((uintptr_t)pa);
+}
+
+// The out-of-place block loop (zrc4_crypt_to_*): crypt_blocks_asm with one
+// difference, the address of every load is the store pointer plus the lane's
+// 64-bit `delta` = source - destination (ZL_SRC_DELTA, one VALU add per
+// block; delta is a multiple of 16, so loads stay 16-byte aligned).  Loads,
+// stores and every vmcnt count are crypt_blocks_asm's: four loads and four
+// stores per block.  On entry A holds (or is loading) block 0 OF THE SOURCE.
+// delta == 0 is exactly the in-place loop.
+__device__ __forceinline__ void crypt_blocks_to_asm(Rc4Lane &st, uint4 *&p, uint32_t nblk, const uint4 (&A)[4],
+                                                    uint64_t delta)
+{
+    u32x4 a0 = {A[0].x, A[0].y, A[0].z, A[0].w}, a1 = {A[1].x, A[1].y, A[1].z, A[1].w};
+    u32x4 a2 = {A[2].x, A[2].y, A[2].z, A[2].w}, a3 = {A[3].x, A[3].y, A[3].z, A[3].w};
+    u32x4 b0, b1, b2, b3, q0, q1, q2, q3;
+    uint64_t pa = (uint64_t)(uintptr_t)p, pn, save;
+    uint32_t i, i1, b, k0, k1, a1s;
+    asm volatile(
+        "s_mov_b64 %[save], exec\n\t"
+        ZL_FIRST_(ZL_SRC_DELTA)
+        "ZL_LOOP_%=:\n\t"
+        ZL_HALF_A_(ZL_SRC_DELTA)
+        "ZL_MID_%=:\n\t"
+        ZL_HALF_B_(ZL_SRC_DELTA)
+        "s_branch ZL_LOOP_%=\n\t"
+        "ZL_DONE_%=:\n\t"
+        "s_mov_b64 exec, %[save]\n\t"
+        : [ya] "+v"(st.ya), [ta] "+v"(st.ta), [x0] "+v"(st.x0), [x1] "+v"(st.x1),
+          [a0] "+v"(st.a0), [a1] "=&v"(a1s), [b] "=&v"(b), [k0] "=&v"(k0), [k1] "=&v"(k1),
+          "+{v[88:89]}"(pa), "=&{v[90:91]}"(pn), [i] "=&s"(i), [i1] "=&s"(i1), [save] "=&s"(save),
+          "+{v[40:43]}"(a0), "+{v[44:47]}"(a1), "+{v[48:51]}"(a2), "+{v[52:55]}"(a3),
+          "=&{v[56:59]}"(b0), "=&{v[60:63]}"(b1), "=&{v[64:67]}"(b2), "=&{v[68:71]}"(b3),
+          "=&{v[72:75]}"(q0), "=&{v[76:79]}"(q1), "=&{v[80:83]}"(q2), "=&{v[84:87]}"(q3)
+        : [nblk] "v"(nblk), [c100] "s"(0x100u), [dl] "v"(delta)
         : "memory", "vcc", "scc");
     p = reinterpret_cast<uint4 *>((uintptr_t)pa);
 }
@@ -593,19 +637,46 @@ __device__ __forceinline__ void issue_block_asm(uint4 (&A)[4], const uint8_t *ms
     A[3] = make_uint4(a3[0], a3[1], a3[2], a3[3]);
 }
 
+// The I/O form of a crypt kernel (last template parameter of the window, half-
+// group, whole-group and declared kernels):
+//   kIoInPlace  the span is read, XORed and written back (zrc4_crypt_*);
+//   kIoKs       write-only keystream (zrc4_keystream_*): the span is stored
+//               and never read;
+//   kIoTo       out of place (zrc4_crypt_to_*): entry i reads its SOURCE span
+//               and stores the XOR to its destination span; the destination
+//               is never read and the source never written.
+enum CryptIo : int { kIoInPlace = 0, kIoKs = 1, kIoTo = 2 };
+
 // Crypt one lane's message in place: unaligned head bytes, 64-byte blocks
 // (crypt_blocks_asm), 16-byte chunks, tail bytes.  If `pre` is set, A already
 // holds the first 64-byte block (issued by the caller ahead of the LDS fill).
-// KS (zrc4_keystream_*): the same walk STORES the keystream and reads no byte
-// of msg (A and pre are unused).
-template <bool KS = false>
+// kIoKs (zrc4_keystream_*): the same walk STORES the keystream and reads no
+// byte of msg (A and pre are unused).
+// kIoTo (zrc4_crypt_to_*): msg is the destination, and every load comes from
+// msg + delta (delta = source - destination, two's complement).  The walk is
+// set by the destination's alignment.  delta % 16 == 0: the same walk, with
+// 16-byte loads from the source (crypt_blocks_to_asm; `pre`: A holds the
+// source's first block).  Otherwise no 16-byte load of the source would be
+// aligned, and the whole message goes byte by byte (one byte load, one PRGA
+// step, one byte store): correct at any pair of alignments, about as fast as
+// the head and tail loops, and never a read of the destination.
+template <int IO = kIoInPlace>
 __device__ __forceinline__ void crypt_message(uint8_t *S, Rc4Lane &st, uint8_t *msg,
-                                              uint32_t len, uint4 (&A)[4], bool pre)
+                                              uint32_t len, uint4 (&A)[4], bool pre, uint64_t delta = 0)
 {
+    constexpr bool KS = IO == kIoKs, TO = IO == kIoTo;
+    if constexpr (TO) {
+        if (delta & 15u) {
+            const uint8_t *s = reinterpret_cast<const uint8_t *>((uintptr_t)msg + delta);
+            for (uint32_t i = 0; i < len; ++i) msg[i] = s[i] ^ (uint8_t)prga_step(S, st);
+            return;
+        }
+    }
     const uint32_t head = head_bytes(msg, len);
     for (uint32_t i = 0; i < head; ++i) {
         const uint8_t k = (uint8_t)prga_step(S, st);
         if constexpr (KS) msg[i] = k;
+        else if constexpr (TO) msg[i] = *reinterpret_cast<const uint8_t *>((uintptr_t)(msg + i) + delta) ^ k;
         else msg[i] ^= k;
     }
     msg += head;
@@ -616,6 +687,9 @@ __device__ __forceinline__ void crypt_message(uint8_t *S, Rc4Lane &st, uint8_t *
     if (nblk) {
         if constexpr (KS) {
             keystream_blocks_asm(st, p, nblk);
+        } else if constexpr (TO) {
+            if (!pre) issue_block_asm(A, reinterpret_cast<const uint8_t *>((uintptr_t)p + delta));
+            crypt_blocks_to_asm(st, p, nblk, A, delta);
         } else {
             if (!pre) issue_block_asm(A, reinterpret_cast<const uint8_t *>(p));
             crypt_blocks_asm(st, p, nblk, A);
@@ -624,6 +698,7 @@ __device__ __forceinline__ void crypt_message(uint8_t *S, Rc4Lane &st, uint8_t *
     uint32_t rem = len & 63u;
     while (rem >= 16u) {
         if constexpr (KS) *p = xor16(S, st, make_uint4(0u, 0u, 0u, 0u));
+        else if constexpr (TO) *p = xor16(S, st, *reinterpret_cast<const uint4 *>((uintptr_t)p + delta));
         else *p = xor16(S, st, *p);
         ++p;
         rem -= 16u;
@@ -632,6 +707,7 @@ __device__ __forceinline__ void crypt_message(uint8_t *S, Rc4Lane &st, uint8_t *
     for (uint32_t i = 0; i < rem; ++i) {
         const uint8_t k = (uint8_t)prga_step(S, st);
         if constexpr (KS) t[i] = k;
+        else if constexpr (TO) t[i] = *reinterpret_cast<const uint8_t *>((uintptr_t)(t + i) + delta) ^ k;
         else t[i] ^= k;
     }
 }
@@ -1154,6 +1230,23 @@ struct FrameArgs {
     uint32_t *npk, *used, *status, *pkt_len;
 };
 
+// The out-of-place kernels (kIoTo) are never framed, and take their two extra
+// pointers in the FrameArgs position of the argument list: the argument
+// layout -- and with it the machine code -- of every other instantiation is
+// what it was before the form existed.
+struct ToArgs {
+    const uint8_t *src;        // source of entry e = src + src_off[e] ...
+    const uint64_t *src_off;   // ... len[e] bytes
+    uint64_t unused[5];
+};
+static_assert(sizeof(ToArgs) == sizeof(FrameArgs), "ToArgs stands where FrameArgs does");
+template <int IO>
+struct AuxArgsOf { using type = FrameArgs; };
+template <>
+struct AuxArgsOf<kIoTo> { using type = ToArgs; };
+template <int IO>
+using AuxArgs = typename AuxArgsOf<IO>::type;
+
 __device__ __forceinline__ uint32_t load_le32(const uint8_t *p)
 {
     return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
@@ -1288,18 +1381,20 @@ struct BucketGroups {
     uint32_t g[kBodyMaxBuckets];
 };
 
-template <int MODE, bool FRAME, bool HALF, bool DECL = false, bool KS = false>
+template <int MODE, bool FRAME, bool HALF, bool DECL = false, int IO = kIoInPlace>
 __device__ __forceinline__ void
 crypt_body(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy,
            const uint32_t *__restrict__ ids, uint32_t first_slot,
            uint8_t *__restrict__ payload, const uint64_t *__restrict__ off,
            const uint32_t *__restrict__ len, uint32_t n, uint32_t capacity,
-           uint32_t *__restrict__ err, uint8_t *__restrict__ sink, const FrameArgs &fr, const Claim &cl,
+           uint32_t *__restrict__ err, uint8_t *__restrict__ sink, const AuxArgs<IO> &fr, const Claim &cl,
            const BucketGroups *dg = nullptr)
 {
+    constexpr bool KS = IO == kIoKs, TO = IO == kIoTo;
     static_assert(!HALF || MODE != kIds, "half-group workgroups run range and grouped batches");
     static_assert(!DECL || MODE == kGrouped, "declared groups are a grouped-batch form");
     static_assert(!KS || (!FRAME && MODE != kIds), "write-only keystream: range and grouped batches, never framed");
+    static_assert(!TO || (!FRAME && MODE != kIds), "out of place: range and grouped batches, never framed");
     __shared__ __attribute__((aligned(16))) uint8_t smem[HALF ? kSmemHalf : kSmemDirect];
     uint8_t *S = smem;
     if (!lds_base_ok(S, err)) return;
@@ -1364,6 +1459,7 @@ crypt_body(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy,
     bool whole;
     uint32_t g, slot, mylen, ent;   // ent: the batch entry this lane runs (kGrouped permutes)
     uint64_t myoff;
+    uint64_t mysoff = 0;            // kIoTo: the entry's source offset
     uint16_t sxy;
     if constexpr (MODE == kRange) {
         // Issued from asm, first: hipcc otherwise sinks these loads below its
@@ -1375,6 +1471,9 @@ crypt_body(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy,
         ent = e;
         mylen = valid ? len[e] : 0u;
         myoff = valid ? off[e] : 0u;
+        // (one more load behind the image: the counted wait below then waits
+        // for the image and for the oldest of these, never for less)
+        if constexpr (TO) mysoff = valid ? fr.src_off[e] : 0u;
         slot = valid ? first_slot + e : ZRC4_INVALID;
         sxy = valid ? xy[slot] : (uint16_t)0;
     } else if constexpr (MODE == kGrouped) {
@@ -1515,6 +1614,10 @@ crypt_body(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy,
         ent = te[j];
         mylen = ent != ZRC4_INVALID ? tl[j] : 0u;
         myoff = ent != ZRC4_INVALID ? to[j] : 0u;
+        // kIoTo: the source offset of the lane's entry, loaded once the slot
+        // table names it (a dependent round trip, beside the image's where
+        // the guess missed; the declared prologue's asm loads stay as they are)
+        if constexpr (TO) mysoff = ent != ZRC4_INVALID ? fr.src_off[ent] : 0u;
         slot = g * 256u + j;
         sxy = xyw;
         if (!DECL && (!have || gw != g)) {               // wave-uniform: the guess missed
@@ -1555,8 +1658,14 @@ crypt_body(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy,
 
     uint8_t *msg = payload + myoff;
     uint4 A[4];
-    // (KS stores keystream and loads no payload: there is no block 0 to issue)
-    const bool pre = !KS && active && mylen >= 64u && head_bytes(msg, mylen) == 0u;
+    // kIoTo: source - destination of this lane's entry; every load is msg + delta
+    uint64_t delta = 0;
+    if constexpr (TO) delta = (uint64_t)(uintptr_t)(fr.src + mysoff) - (uint64_t)(uintptr_t)msg;
+    const uint8_t *blk0 = reinterpret_cast<const uint8_t *>((uintptr_t)msg + delta);
+    // (KS stores keystream and loads no payload: there is no block 0 to issue;
+    // an out-of-place entry whose addresses are not congruent mod 16 goes byte
+    // by byte, crypt_message)
+    const bool pre = !KS && active && mylen >= 64u && head_bytes(msg, mylen) == 0u && (!TO || (delta & 15u) == 0u);
     if constexpr (MODE != kIds) {
         // The image was issued before the entry loads still in flight (kRange:
         // len, off and x/y; kGrouped: x/y).  Waited on every path (the
@@ -1579,7 +1688,7 @@ crypt_body(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy,
 #pragma unroll
             for (int i = 0; i < 16; ++i) img[i] = src[i * 256 + tid];
         }
-        if (pre) issue_block_asm(A, msg);
+        if (pre) issue_block_asm(A, TO ? blk0 : msg);
 #pragma unroll
         for (int i = 0; i < 16; ++i) *reinterpret_cast<uint4 *>(S + i * 4096 + vo0) = img[i];
         __syncthreads();
@@ -1590,7 +1699,7 @@ crypt_body(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy,
             }
         }
     } else {
-        if (pre) issue_block_asm(A, msg);
+        if (pre) issue_block_asm(A, TO ? blk0 : msg);
         if (active) gather_column(S, col, arena, slot);
     }
     stamp(ts, 1);
@@ -1598,7 +1707,7 @@ crypt_body(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy,
     if (active) {
         Rc4Lane st;
         lane_init(st, S, col, sxy);
-        crypt_message<KS>(S, st, msg, mylen, A, pre);
+        crypt_message<IO>(S, st, msg, mylen, A, pre, delta);
         xy[slot] = lane_xy(st);
     }
     if constexpr (FRAME) {
@@ -1629,30 +1738,30 @@ crypt_body(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy,
 #endif
 }
 
-template <int MODE, bool FRAME = false, bool KS = false>
+template <int MODE, bool FRAME = false, int IO = kIoInPlace>
 __global__ void __launch_bounds__(256, 2)
 crypt_kernel(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy,
              const uint32_t *__restrict__ ids, uint32_t first_slot,
              uint8_t *__restrict__ payload, const uint64_t *__restrict__ off,
              const uint32_t *__restrict__ len, uint32_t n, uint32_t capacity,
-             uint32_t *__restrict__ err, uint8_t *__restrict__ sink, FrameArgs fr = FrameArgs{},
+             uint32_t *__restrict__ err, uint8_t *__restrict__ sink, AuxArgs<IO> fr = AuxArgs<IO>{},
              Claim cl = Claim{})
 {
-    crypt_body<MODE, FRAME, false, false, KS>(arena, xy, ids, first_slot, payload, off, len, n, capacity, err, sink, fr,
+    crypt_body<MODE, FRAME, false, false, IO>(arena, xy, ids, first_slot, payload, off, len, n, capacity, err, sink, fr,
                                               cl);
 }
 
 // The grouped forms with declared bucket groups (zrc4_crypt_grouped_declared,
 // 33..256 buckets): the groups in the kernel arguments.
-template <bool FRAME, bool HALF, bool KS = false>
+template <bool FRAME, bool HALF, int IO = kIoInPlace>
 __global__ void __launch_bounds__(256u, HALF ? 1 : 2)
 crypt_decl_kernel(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy,
                   const uint32_t *__restrict__ ids, uint8_t *__restrict__ payload,
                   const uint64_t *__restrict__ off, const uint32_t *__restrict__ len, uint32_t n,
-                  uint32_t capacity, uint32_t *__restrict__ err, uint8_t *__restrict__ sink, FrameArgs fr,
+                  uint32_t capacity, uint32_t *__restrict__ err, uint8_t *__restrict__ sink, AuxArgs<IO> fr,
                   Claim cl, BucketGroups dg)
 {
-    crypt_body<kGrouped, FRAME, HALF, true, KS>(arena, xy, ids, 0u, payload, off, len, n, capacity, err, sink, fr, cl,
+    crypt_body<kGrouped, FRAME, HALF, true, IO>(arena, xy, ids, 0u, payload, off, len, n, capacity, err, sink, fr, cl,
                                                 &dg);
 }
 
@@ -1661,16 +1770,16 @@ crypt_decl_kernel(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy,
 // which the two waves that work are picked by SIMD (crypt_body).
 constexpr uint32_t kHalfBlock = 256u;
 
-template <int MODE, bool FRAME = false, bool KS = false>
+template <int MODE, bool FRAME = false, int IO = kIoInPlace>
 __global__ void __launch_bounds__(kHalfBlock, 1)
 crypt_half_kernel(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy,
                   const uint32_t *__restrict__ ids, uint32_t first_slot,
                   uint8_t *__restrict__ payload, const uint64_t *__restrict__ off,
                   const uint32_t *__restrict__ len, uint32_t n, uint32_t capacity,
-                  uint32_t *__restrict__ err, uint8_t *__restrict__ sink, FrameArgs fr = FrameArgs{},
+                  uint32_t *__restrict__ err, uint8_t *__restrict__ sink, AuxArgs<IO> fr = AuxArgs<IO>{},
                   Claim cl = Claim{})
 {
-    crypt_body<MODE, FRAME, true, false, KS>(arena, xy, ids, first_slot, payload, off, len, n, capacity, err, sink, fr,
+    crypt_body<MODE, FRAME, true, false, IO>(arena, xy, ids, first_slot, payload, off, len, n, capacity, err, sink, fr,
                                              cl);
 }
 
@@ -3052,6 +3161,46 @@ span_fill_kernel(const uint32_t *__restrict__ ids, uint8_t *__restrict__ out, co
         uint4 *q = reinterpret_cast<uint4 *>(p + head);
         for (uint32_t u = lane; u < units; u += 64u) q[u] = make_uint4(0u, 0u, 0u, 0u);
         if (lane < tail) p[head + 16u * units + lane] = 0;
+    }
+}
+
+// ---------------------------------------------------------------------------
+// span_copy_kernel: copies the source span of every entry a crypt launch would
+// run into its destination span (zrc4_crypt_to_* with more groups than CUs:
+// the persistent kernel has no out-of-place form, so the sources are copied on
+// the same stream just before it and it crypts the destinations in place).
+// Skipped entries keep their destination bytes, exactly as in
+// span_fill_kernel; so does an entry whose source and destination are the
+// same address (the in-place case: nothing to copy).  One wave per entry,
+// grid-stride.  Addresses congruent mod 16: bytes up to the destination's first
+// 16-byte boundary, 16-byte units, tail bytes.  Otherwise bytes, 64 per wave
+// and step.  Loads from the source and stores to the destination only,
+// nothing outside [dst_off, dst_off + len).
+// ---------------------------------------------------------------------------
+__global__ void __launch_bounds__(256)
+span_copy_kernel(const uint32_t *__restrict__ ids, const uint8_t *src, const uint64_t *__restrict__ src_off,
+                 uint8_t *dst, const uint64_t *__restrict__ dst_off, const uint32_t *__restrict__ len, uint32_t n,
+                 uint32_t capacity)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t waves = (uint64_t)gridDim.x * 4u;
+    for (uint64_t e = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6); e < n; e += waves) {
+        const uint32_t L = len[e];
+        if (L == 0u || (ids && ids[e] >= capacity)) continue;
+        uint8_t *p = dst + dst_off[e];
+        const uint8_t *s = src + src_off[e];
+        if (s == p) continue;
+        if (((uintptr_t)s ^ (uintptr_t)p) & 15u) {
+            for (uint32_t i = lane; i < L; i += 64u) p[i] = s[i];
+            continue;
+        }
+        const uint32_t head = head_bytes(p, L);
+        if (lane < head) p[lane] = s[lane];
+        const uint32_t body = L - head, units = body >> 4, tail = body & 15u;
+        uint4 *q = reinterpret_cast<uint4 *>(p + head);
+        const uint4 *sq = reinterpret_cast<const uint4 *>(s + head);
+        for (uint32_t u = lane; u < units; u += 64u) q[u] = sq[u];
+        if (lane < tail) p[head + 16u * units + lane] = s[head + 16u * units + lane];
     }
 }
 

@@ -230,7 +230,7 @@ struct zrc4_ks {
         int rc = R.t.build(es) ? (set_device(c) ? ZRC4_ERR_HIP
                                                 : launch_crypt(c, zrc4::kGrouped, R.t.ids.p, 0, base, R.t.off.p,
                                                                R.t.len.p, R.t.n, sB, nullptr, R.t.groups.data(), true,
-                                                               true))
+                                                               zrc4::kIoKs))
                                : ZRC4_ERR_OUT_OF_MEMORY;
         if (rc != ZRC4_OK) {                      // nothing queued: the levels go back
             for (const KsEntry &e : es) lv[e.slot].pend -= e.len;

@@ -229,20 +229,34 @@ struct WinGroups {
 //             stream's bytes are decrypted; grouped entries that decrypt
 //             nothing (idle ids, length 0, idle buckets) by lane q of the
 //             bucket's workgroup q (entries q + 64r), on the raw bytes.
-//   KS:       write-only keystream (zrc4_keystream_*): no payload prefetch at
+//   kIoKs:    write-only keystream (zrc4_keystream_*): no payload prefetch at
 //             all, and the XOR pass is a STORE of the LDS keystream ring to
 //             the span (16-byte units where the span start is 16-byte
 //             aligned, bytes otherwise; never a read-modify-write).  The
 //             grouped claim's ordering is unchanged: nothing is stored
 //             before claim_wait.  Never combined with FRAME.
-template <int MODE, bool FRAME, bool DECL = false, bool KS = false>
+//   kIoTo:    out of place (zrc4_crypt_to_*; IO is the last template
+//             parameter, kIoKs the form above).  Both prefetches read the
+//             entry's SOURCE span and the XOR pass stores prefetch ^ ring to
+//             the destination span: 16-byte units when source and
+//             destination are both 16-byte aligned (congruent mod 16, the
+//             destination aligned), otherwise dst[pos] = src[pos] ^ ring byte
+//             by byte -- never a read of the destination.  Grouped: the
+//             source offsets ride with the entries' ids, lengths and offsets
+//             (the same round trip) into a fourth slot table in the ring's
+//             free last quarter; loading src_off[te[kb]] after the table
+//             build would put a dependent global round trip in front of the
+//             first prefetch, against one LDS write and read here.  The
+//             pointers arrive in the FrameArgs position (ToArgs).
+template <int MODE, bool FRAME, bool DECL = false, int IO = kIoInPlace>
 __global__ void __launch_bounds__(64)
 crypt_win_kernel(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy, const uint32_t *__restrict__ ids,
                  uint32_t first_slot, uint8_t *__restrict__ payload, const uint64_t *__restrict__ off,
                  const uint32_t *__restrict__ len, uint32_t n, uint32_t capacity, uint32_t *__restrict__ err,
-                 uint8_t *__restrict__ sink, FrameArgs fr, Claim cl, WinGroups dg = WinGroups{})
+                 uint8_t *__restrict__ sink, AuxArgs<IO> fr, Claim cl, WinGroups dg = WinGroups{})
 {
-    static_assert(!KS || !FRAME, "write-only keystream is never framed");
+    constexpr bool KS = IO == kIoKs, TO = IO == kIoTo;
+    static_assert(!(KS || TO) || !FRAME, "the write-only and out-of-place forms are never framed");
     Stamps ts;                                   // ZRC4_TIMING builds only (zrc4_kernels.hpp)
     stamp(ts, 0);
     __shared__ __attribute__((aligned(1024))) uint32_t Mk[kWinStreams * 256];
@@ -259,7 +273,7 @@ crypt_win_kernel(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy, const u
     const uint32_t lane = threadIdx.x, l = lane & 15u, b = lane >> 4;
     const uint32_t kb = ((q >> 5) << 7) + (q & 31u) + 32u * b;             // group-lane of this lane's stream
     uint32_t slot, L = 0, ent = 0;                                         // ent: this stream's batch entry
-    uint64_t O = 0;
+    uint64_t O = 0, SO = 0;                                                // SO: kIoTo's source offset
     bool valid;
     uint32_t rows[4];
     uint32_t sxy, sxy_g;                                                   // sxy_g: kGrouped's x/y on the guess
@@ -279,6 +293,7 @@ crypt_win_kernel(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy, const u
         if (valid) {
             L = len[e];
             O = off[e];
+            if constexpr (TO) SO = fr.src_off[e];
         }
         sxy = valid ? xy[slot] : 0u;
     } else {
@@ -286,8 +301,10 @@ crypt_win_kernel(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy, const u
         uint32_t *tl = te + 256;                                              // length
         uint64_t *to = reinterpret_cast<uint64_t *>(Ring + 2048);             // offset
         uint32_t *fl = reinterpret_cast<uint32_t *>(Ring + 4096);             // 256-bit seen map, bad flag
+        uint64_t *tso = reinterpret_cast<uint64_t *>(Ring + 6144);            // kIoTo: source offset
+        static_assert(kWinStreams * kWinRing >= 8192, "the slot tables use the ring's 8 KiB");
         uint32_t idq[4], lq[4];
-        uint64_t oq[4];
+        uint64_t oq[4], soq[4];
         bool bq[4];
         uint32_t gw = ZRC4_INVALID;
         // all twelve entry loads first, the checks after (a check inside the
@@ -299,6 +316,7 @@ crypt_win_kernel(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy, const u
             idq[r] = v ? ids[e] : ZRC4_INVALID;
             lq[r] = v ? len[e] : 0u;
             oq[r] = v ? off[e] : 0u;
+            if constexpr (TO) soq[r] = v ? fr.src_off[e] : 0u;
         }
         if constexpr (DECL) {
             // the declared group: image, x/y and claim leave right behind the
@@ -370,6 +388,7 @@ crypt_win_kernel(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy, const u
                 te[kk] = wg * kGroup + lane + 64u * r;
                 tl[kk] = lq[r];
                 to[kk] = oq[r];
+                if constexpr (TO) tso[kk] = soq[r];
             }
         }
         __syncthreads();
@@ -379,12 +398,16 @@ crypt_win_kernel(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy, const u
         if (valid) {
             L = tl[kb];
             O = to[kb];
+            if constexpr (TO) SO = tso[kb];
         }
         bad = fl[8] != 0u;
     }
     uint8_t *img = arena + (size_t)(slot >> 8) * kGroupBytes + 4u * q;
     uint8_t *msg = payload + O;
-    const bool aligned = ((uintptr_t)msg & 15u) == 0u;
+    // kIoTo: every load reads smsg (the entry's source), every store writes msg
+    const uint8_t *smsg = msg;
+    if constexpr (TO) smsg = fr.src + SO;
+    const bool aligned = (((uintptr_t)msg | (uintptr_t)smsg) & 15u) == 0u;
 
     // The S-boxes into LDS (the wave's 4 streams share every dword of the
     // image column) and the markers cleared.  kGrouped: before the payload
@@ -433,9 +456,9 @@ crypt_win_kernel(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy, const u
         for (uint32_t u = 0; u < kWinUnits; ++u) {
             const uint32_t pos = 16u * (l + kWinLanes * u);
             if constexpr (MODE == kGrouped)
-                pre[u] = *reinterpret_cast<const uint4 *>(aligned && pos + 16u <= L ? msg + pos : sink + 16u * lane);
+                pre[u] = *reinterpret_cast<const uint4 *>(aligned && pos + 16u <= L ? smsg + pos : sink + 16u * lane);
             else if (aligned && pos + 16u <= L)
-                pre[u] = *reinterpret_cast<const uint4 *>(msg + pos);
+                pre[u] = *reinterpret_cast<const uint4 *>(smsg + pos);
         }
     }
     if constexpr (MODE == kGrouped) cold = claim_part_async(cl, gclaim, q, wg);
@@ -505,7 +528,13 @@ crypt_win_kernel(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy, const u
                 }
             }
             const uint32_t tpos = c0 + ((c1 - c0) & ~15u) + l;                  // ragged tail: < 16 bytes
-            if (tpos < c1) msg[tpos] ^= R[tpos & (kWinRing - 1u)];
+            if constexpr (TO) {
+                if (tpos < c1) msg[tpos] = smsg[tpos] ^ R[tpos & (kWinRing - 1u)];
+            } else {
+                if (tpos < c1) msg[tpos] ^= R[tpos & (kWinRing - 1u)];
+            }
+        } else if constexpr (TO) {
+            for (uint32_t pos = c0 + l; pos < c1; pos += kWinLanes) msg[pos] = smsg[pos] ^ R[pos & (kWinRing - 1u)];
         } else {
             for (uint32_t pos = c0 + l; pos < c1; pos += kWinLanes) msg[pos] ^= R[pos & (kWinRing - 1u)];
         }
@@ -515,7 +544,7 @@ crypt_win_kernel(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy, const u
 #pragma unroll
             for (uint32_t u = 0; u < kWinUnits; ++u) {
                 const uint32_t pos = n0 + 16u * (l + kWinLanes * u);
-                if (aligned && pos + 16u <= L) pre[u] = *reinterpret_cast<const uint4 *>(msg + pos);
+                if (aligned && pos + 16u <= L) pre[u] = *reinterpret_cast<const uint4 *>(smsg + pos);
             }
         }
     }
