@@ -188,6 +188,30 @@ class Context:
                                               _ptr(dst_off), _ptr(length), n, _stream(stream)),
               "zrc4_crypt_to_grouped")
 
+    def crypt_to_range_rounds(self, first_slot: int, src, src_off, dst, dst_off, length, n: int, rounds: int,
+                              stream=None) -> None:
+        """zrc4_crypt_to_range_rounds: `rounds` successive crypt_to_range calls
+        in one launch; src_off, dst_off and length hold rounds * n entries,
+        round-major (entry i of round r at r * n + i)."""
+        check(self._lib.zrc4_crypt_to_range_rounds(self._h, int(first_slot), _ptr(src), _ptr(src_off), _ptr(dst),
+                                                   _ptr(dst_off), _ptr(length), int(n), int(rounds), _stream(stream)),
+              "zrc4_crypt_to_range_rounds")
+
+    def crypt_to_grouped_rounds(self, src, src_off, dst, dst_off, length, ids, n: int, rounds: int,
+                                bucket_group=None, stream=None) -> None:
+        """zrc4_crypt_to_grouped_rounds: `rounds` successive crypt_to_grouped
+        calls in one launch over the same ids (and declared groups); the
+        other tables are round-major as in crypt_to_range_rounds."""
+        n = int(n)
+        bg = None
+        if bucket_group is not None:
+            bg = np.ascontiguousarray(bucket_group, dtype=np.uint32)
+            if bg.size < -(-n // GROUP_SLOTS):
+                raise ValueError("bucket_group needs one entry per 256-entry bucket")
+        check(self._lib.zrc4_crypt_to_grouped_rounds(self._h, _ptr(ids), _ptr(bg), _ptr(src), _ptr(src_off),
+                                                     _ptr(dst), _ptr(dst_off), _ptr(length), n, int(rounds),
+                                                     _stream(stream)), "zrc4_crypt_to_grouped_rounds")
+
     @staticmethod
     def _frame(frame: dict) -> FrameArgs:
         return FrameArgs(_ptr(frame["off"]), _ptr(frame["len"]), int(frame["bound"]), int(frame.get("max_packets", 0)),

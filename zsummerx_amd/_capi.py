@@ -47,6 +47,8 @@ SIGNATURES = [
     ("zrc4_keystream_grouped", C.c_int, [_P, _P, _P, _P, _P, _P, C.c_uint32, _P]),
     ("zrc4_crypt_to_range", C.c_int, [_P, C.c_uint32, _P, _P, _P, _P, _P, C.c_uint32, _P]),
     ("zrc4_crypt_to_grouped", C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, C.c_uint32, _P]),
+    ("zrc4_crypt_to_range_rounds", C.c_int, [_P, C.c_uint32, _P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, _P]),
+    ("zrc4_crypt_to_grouped_rounds", C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, _P]),
     ("zrc4_crypt_range_frame",C.c_int, [_P, C.c_uint32, _P, _P, _P, C.c_uint32, _P, _P]),
     ("zrc4_crypt_grouped_frame", C.c_int, [_P, _P, _P, _P, _P, C.c_uint32, _P, _P]),
     ("zrc4_ksa_host", C.c_int, [_P, _P, _P, C.c_size_t, _P, _P, C.c_uint32]),

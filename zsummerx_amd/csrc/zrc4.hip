@@ -122,19 +122,41 @@ constexpr size_t kZeroCopyMax = 256u << 10;   // *_host batches up to this size 
 // + off[i].  Again the window, half- and whole-group kernels have the form;
 // ahead of the persistent kernel span_copy_kernel copies the sources into the
 // destinations on the same stream, and the in-place launch runs over those.
+//
+// `io` = zrc4::kIoToRounds with `rounds` >= 2 (zrc4_crypt_to_*_rounds): off,
+// len and src_off hold rounds * n entries, round-major, and every slot runs
+// its `rounds` entries in order in ONE launch of the half-group, whole-group
+// or declared kernel -- also at 32 groups and fewer: the window kernel has no
+// rounds form.  With more groups than CUs the rounds are `rounds` successive
+// kIoTo calls on the stream, from the loop below.
 int launch_crypt(zrc4_ctx *c, int mode, const uint32_t *ids, uint32_t first_slot, uint8_t *payload,
                  const uint64_t *off, const uint32_t *len, uint32_t n, hipStream_t s,
                  const zrc4::FrameArgs *fr = nullptr, const uint32_t *decl = nullptr, bool decl_trusted = false,
-                 int io = zrc4::kIoInPlace, const uint8_t *src = nullptr, const uint64_t *src_off = nullptr)
+                 int io = zrc4::kIoInPlace, const uint8_t *src = nullptr, const uint64_t *src_off = nullptr,
+                 uint32_t rounds = 1)
 {
     if (n == 0) return ZRC4_OK;
-    const bool ks = io == zrc4::kIoKs, to = io == zrc4::kIoTo;
-    if ((ks || to) && (fr || mode == zrc4::kIds)) return ZRC4_ERR_INVALID_ARG;
-    if (to && (!src || !src_off)) return ZRC4_ERR_INVALID_ARG;
+    const bool ks = io == zrc4::kIoKs, to = io == zrc4::kIoTo, tor = io == zrc4::kIoToRounds;
+    if ((ks || to || tor) && (fr || mode == zrc4::kIds)) return ZRC4_ERR_INVALID_ARG;
+    if ((to || tor) && (!src || !src_off)) return ZRC4_ERR_INVALID_ARG;
+    if (tor && (rounds < 2u || (uint64_t)n * rounds > 0xFFF00000u)) return ZRC4_ERR_INVALID_ARG;
     zrc4::ToArgs ta{};
     ta.src = src;
     ta.src_off = src_off;
+    ta.rounds = rounds;
+    ta.stride = n;
     if (mode == zrc4::kRange && (uint64_t)first_slot + n > c->capacity) return ZRC4_ERR_SLOT_RANGE;
+    if (tor && (n + zrc4::kGroup - 1) / zrc4::kGroup > (uint32_t)c->num_cus) {
+        // the persistent kernel has no out-of-place form, so no rounds form
+        // either: one two-launch kIoTo sequence per round (claims per round)
+        for (uint32_t r = 0; r < rounds; ++r) {
+            const size_t at = (size_t)r * n;
+            const int rc = launch_crypt(c, mode, ids, first_slot, payload, off + at, len + at, n, s, nullptr, decl,
+                                        decl_trusted, zrc4::kIoTo, src, src_off + at);
+            if (rc != ZRC4_OK) return rc;
+        }
+        return ZRC4_OK;
+    }
     zrc4::Claim cl{nullptr, 0u, nullptr};
     if (mode == zrc4::kGrouped) {
         // a fresh tag per grouped launch; on the 32-bit wrap the words are
@@ -155,7 +177,7 @@ int launch_crypt(zrc4_ctx *c, int mode, const uint32_t *ids, uint32_t first_slot
     // Few aligned groups (at most kWinMaxBuckets, so that declared groups
     // travel in WinGroups): 16 lanes per stream (speculative windows,
     // crypt_win_kernel), one wave per 4 streams, 64 workgroups per group.
-    if (grid <= zrc4::kWinMaxBuckets &&
+    if (!tor && grid <= zrc4::kWinMaxBuckets &&
         ((mode == zrc4::kRange && (first_slot & 255u) == 0u) || mode == zrc4::kGrouped)) {
         const dim3 wgrid(64u * grid), wblk(64);
         const zrc4::FrameArgs fa = fr ? *fr : zrc4::FrameArgs{};
@@ -205,7 +227,11 @@ int launch_crypt(zrc4_ctx *c, int mode, const uint32_t *ids, uint32_t first_slot
     hipLaunchKernelGGL((zrc4::crypt_decl_kernel<FRAME_, HALF_, IO_>), GRID_, BLK_, 0, s, c->arena, c->xy, ids, \
                        payload, off, len, n, c->capacity, c->err, c->sink, AUX_, cl, dg)
 #define ZRC4_DECL(FRAME_, HALF_, IO_, GRID_, BLK_) ZRC4_DECL_(FRAME_, HALF_, IO_, GRID_, BLK_, fa)
-        if (half && to)
+        if (half && tor)
+            ZRC4_DECL_(false, true, zrc4::kIoToRounds, dim3(2u * grid), dim3(zrc4::kHalfBlock), ta);
+        else if (tor)
+            ZRC4_DECL_(false, false, zrc4::kIoToRounds, dim3(grid), blk, ta);
+        else if (half && to)
             ZRC4_DECL_(false, true, zrc4::kIoTo, dim3(2u * grid), dim3(zrc4::kHalfBlock), ta);
         else if (to)
             ZRC4_DECL_(false, false, zrc4::kIoTo, dim3(grid), blk, ta);
@@ -259,7 +285,14 @@ int launch_crypt(zrc4_ctx *c, int mode, const uint32_t *ids, uint32_t first_slot
         const dim3 hblk(zrc4::kHalfBlock);
         const dim3 hgrid(mode == zrc4::kGrouped ? 2u * grid : (n + zrc4::kGroup / 2 - 1) / (zrc4::kGroup / 2));
         const zrc4::FrameArgs fa = fr ? *fr : zrc4::FrameArgs{};
-        if (to && mode == zrc4::kRange)
+        if (tor && mode == zrc4::kRange)
+            hipLaunchKernelGGL((zrc4::crypt_half_kernel<zrc4::kRange, false, zrc4::kIoToRounds>), hgrid, hblk, 0, s,
+                               c->arena, c->xy, ids, first_slot, payload, off, len, n, c->capacity, c->err, c->sink, ta);
+        else if (tor)
+            hipLaunchKernelGGL((zrc4::crypt_half_kernel<zrc4::kGrouped, false, zrc4::kIoToRounds>), hgrid, hblk, 0, s,
+                               c->arena, c->xy, ids, first_slot, payload, off, len, n, c->capacity, c->err, c->sink, ta,
+                               cl);
+        else if (to && mode == zrc4::kRange)
             hipLaunchKernelGGL((zrc4::crypt_half_kernel<zrc4::kRange, false, zrc4::kIoTo>), hgrid, hblk, 0, s, c->arena,
                                c->xy, ids, first_slot, payload, off, len, n, c->capacity, c->err, c->sink, ta);
         else if (to)
@@ -309,6 +342,16 @@ int launch_crypt(zrc4_ctx *c, int mode, const uint32_t *ids, uint32_t first_slot
             hipLaunchKernelGGL((zrc4::crypt_kernel<zrc4::kGrouped, false, zrc4::kIoKs>), dim3(grid), blk, 0, s,
                                c->arena, c->xy, ids, first_slot, payload, off, len, n, c->capacity, c->err, c->sink,
                                zrc4::FrameArgs{}, cl);
+        return hipGetLastError() == hipSuccess ? ZRC4_OK : ZRC4_ERR_LAUNCH;
+    }
+    if (tor) {                                           // (never the persistent kernel: handled above)
+        if (mode == zrc4::kRange)
+            hipLaunchKernelGGL((zrc4::crypt_kernel<zrc4::kRange, false, zrc4::kIoToRounds>), dim3(grid), blk, 0, s,
+                               c->arena, c->xy, ids, first_slot, payload, off, len, n, c->capacity, c->err, c->sink, ta);
+        else
+            hipLaunchKernelGGL((zrc4::crypt_kernel<zrc4::kGrouped, false, zrc4::kIoToRounds>), dim3(grid), blk, 0, s,
+                               c->arena, c->xy, ids, first_slot, payload, off, len, n, c->capacity, c->err, c->sink, ta,
+                               cl);
         return hipGetLastError() == hipSuccess ? ZRC4_OK : ZRC4_ERR_LAUNCH;
     }
     if (to && !stream_kernel) {
@@ -691,6 +734,40 @@ int zrc4_crypt_to_grouped(zrc4_ctx *c, const uint32_t *ids, const uint32_t *buck
     if (rc) return rc;
     return launch_crypt(c, zrc4::kGrouped, ids, 0, dst, dst_off, len, n, (hipStream_t)stream, nullptr, bucket_group,
                         false, zrc4::kIoTo, src, src_off);
+}
+
+int zrc4_crypt_to_range_rounds(zrc4_ctx *c, uint32_t first_slot, const uint8_t *src, const uint64_t *src_off,
+                               uint8_t *dst, const uint64_t *dst_off, const uint32_t *len, uint32_t n, uint32_t rounds,
+                               void *stream)
+{
+    if (!c) return ZRC4_ERR_INVALID_ARG;
+    if (rounds == 0u || rounds > ZRC4_MAX_ROUNDS || (uint64_t)n * rounds > 0xFFF00000u) return ZRC4_ERR_INVALID_ARG;
+    if (rounds == 1u) return zrc4_crypt_to_range(c, first_slot, src, src_off, dst, dst_off, len, n, stream);
+    if (n && (!src || !src_off || !dst || !dst_off || !len)) return ZRC4_ERR_INVALID_ARG;
+    int rc = set_device(c);
+    if (rc) return rc;
+    return launch_crypt(c, zrc4::kRange, nullptr, first_slot, dst, dst_off, len, n, (hipStream_t)stream, nullptr,
+                        nullptr, false, zrc4::kIoToRounds, src, src_off, rounds);
+}
+
+int zrc4_crypt_to_grouped_rounds(zrc4_ctx *c, const uint32_t *ids, const uint32_t *bucket_group, const uint8_t *src,
+                                 const uint64_t *src_off, uint8_t *dst, const uint64_t *dst_off, const uint32_t *len,
+                                 uint32_t n, uint32_t rounds, void *stream)
+{
+    if (!c) return ZRC4_ERR_INVALID_ARG;
+    if (rounds == 0u || rounds > ZRC4_MAX_ROUNDS || (uint64_t)n * rounds > 0xFFF00000u) return ZRC4_ERR_INVALID_ARG;
+    if (rounds == 1u) return zrc4_crypt_to_grouped(c, ids, bucket_group, src, src_off, dst, dst_off, len, n, stream);
+    if (n && (!ids || !src || !src_off || !dst || !dst_off || !len)) return ZRC4_ERR_INVALID_ARG;
+    if (bucket_group) {
+        const uint32_t nb = (uint32_t)(((uint64_t)n + zrc4::kGroup - 1) / zrc4::kGroup);
+        const uint32_t groups = c->capacity / zrc4::kGroup;
+        for (uint32_t b = 0; b < nb; ++b)
+            if (bucket_group[b] >= groups && bucket_group[b] != ZRC4_IDLE_SLOT) return ZRC4_ERR_INVALID_ARG;
+    }
+    int rc = set_device(c);
+    if (rc) return rc;
+    return launch_crypt(c, zrc4::kGrouped, ids, 0, dst, dst_off, len, n, (hipStream_t)stream, nullptr, bucket_group,
+                        false, zrc4::kIoToRounds, src, src_off, rounds);
 }
 
 int zrc4_xor_ring(zrc4_ctx *c, uint8_t *ring, uint32_t ring_cap, const uint32_t *rid,

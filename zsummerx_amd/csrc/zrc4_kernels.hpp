@@ -549,6 +549,35 @@ __device__ __forceinline__ void crypt_blocks_asm(Rc4Lane &st, uint4 *&p, uint32_
 // stores and every vmcnt count are crypt_blocks_asm's: four loads and four
 // stores per block.  On entry A holds (or is loading) block 0 OF THE SOURCE.
 // delta == 0 is exactly the in-place loop.
+// DRAIN (kIoToRounds): the loop leaves its last prefetch in flight -- the
+// harmless re-read into the tuple that is not needed any more -- and four
+// stores behind it.  One launch, one walk: the kernel's next VMEM wait retires
+// it before anything else names those registers.  With rounds, hipcc's code
+// for the pieces, the tail and the next round runs next and took v40..v47 for
+// its temporaries, so the statement itself ends with the vmcnt(4) that retires
+// the prefetch (every exit follows a ZL_STORE, so exactly the four stores are
+// younger) and leaves the stores in flight.
+#define ZL_TO_LOOP(TAILWAIT)                                                                     \
+    asm volatile(                                                                                \
+        "s_mov_b64 %[save], exec\n\t"                                                            \
+        ZL_FIRST_(ZL_SRC_DELTA)                                                                  \
+        "ZL_LOOP_%=:\n\t"                                                                        \
+        ZL_HALF_A_(ZL_SRC_DELTA)                                                                 \
+        "ZL_MID_%=:\n\t"                                                                         \
+        ZL_HALF_B_(ZL_SRC_DELTA)                                                                 \
+        "s_branch ZL_LOOP_%=\n\t"                                                                \
+        "ZL_DONE_%=:\n\t"                                                                        \
+        "s_mov_b64 exec, %[save]\n\t"                                                            \
+        TAILWAIT                                                                                 \
+        : [ya] "+v"(st.ya), [ta] "+v"(st.ta), [x0] "+v"(st.x0), [x1] "+v"(st.x1),                \
+          [a0] "+v"(st.a0), [a1] "=&v"(a1s), [b] "=&v"(b), [k0] "=&v"(k0), [k1] "=&v"(k1),       \
+          "+{v[88:89]}"(pa), "=&{v[90:91]}"(pn), [i] "=&s"(i), [i1] "=&s"(i1), [save] "=&s"(save), \
+          "+{v[40:43]}"(a0), "+{v[44:47]}"(a1), "+{v[48:51]}"(a2), "+{v[52:55]}"(a3),            \
+          "=&{v[56:59]}"(b0), "=&{v[60:63]}"(b1), "=&{v[64:67]}"(b2), "=&{v[68:71]}"(b3),        \
+          "=&{v[72:75]}"(q0), "=&{v[76:79]}"(q1), "=&{v[80:83]}"(q2), "=&{v[84:87]}"(q3)         \
+        : [nblk] "v"(nblk), [c100] "s"(0x100u), [dl] "v"(delta)                                  \
+        : "memory", "vcc", "scc")
+template <bool DRAIN = false>
 __device__ __forceinline__ void crypt_blocks_to_asm(Rc4Lane &st, uint4 *&p, uint32_t nblk, const uint4 (&A)[4],
                                                     uint64_t delta)
 {
@@ -557,26 +586,13 @@ __device__ __forceinline__ void crypt_blocks_to_asm(Rc4Lane &st, uint4 *&p, uint
     u32x4 b0, b1, b2, b3, q0, q1, q2, q3;
     uint64_t pa = (uint64_t)(uintptr_t)p, pn, save;
     uint32_t i, i1, b, k0, k1, a1s;
-    asm volatile(
-        "s_mov_b64 %[save], exec\n\t"
-        ZL_FIRST_(ZL_SRC_DELTA)
-        "ZL_LOOP_%=:\n\t"
-        ZL_HALF_A_(ZL_SRC_DELTA)
-        "ZL_MID_%=:\n\t"
-        ZL_HALF_B_(ZL_SRC_DELTA)
-        "s_branch ZL_LOOP_%=\n\t"
-        "ZL_DONE_%=:\n\t"
-        "s_mov_b64 exec, %[save]\n\t"
-        : [ya] "+v"(st.ya), [ta] "+v"(st.ta), [x0] "+v"(st.x0), [x1] "+v"(st.x1),
-          [a0] "+v"(st.a0), [a1] "=&v"(a1s), [b] "=&v"(b), [k0] "=&v"(k0), [k1] "=&v"(k1),
-          "+{v[88:89]}"(pa), "=&{v[90:91]}"(pn), [i] "=&s"(i), [i1] "=&s"(i1), [save] "=&s"(save),
-          "+{v[40:43]}"(a0), "+{v[44:47]}"(a1), "+{v[48:51]}"(a2), "+{v[52:55]}"(a3),
-          "=&{v[56:59]}"(b0), "=&{v[60:63]}"(b1), "=&{v[64:67]}"(b2), "=&{v[68:71]}"(b3),
-          "=&{v[72:75]}"(q0), "=&{v[76:79]}"(q1), "=&{v[80:83]}"(q2), "=&{v[84:87]}"(q3)
-        : [nblk] "v"(nblk), [c100] "s"(0x100u), [dl] "v"(delta)
-        : "memory", "vcc", "scc");
+    if constexpr (DRAIN)
+        ZL_TO_LOOP("s_waitcnt vmcnt(4)\n\t");
+    else
+        ZL_TO_LOOP("");
     p = reinterpret_cast<uint4 *>((uintptr_t)pa);
 }
+#undef ZL_TO_LOOP
 
 // The write-only block loop (KS: zrc4_keystream_*): the same ping-pong over
 // the pinned A and B tuples, exec shrinking as lanes run out of blocks, with
@@ -637,6 +653,32 @@ __device__ __forceinline__ void issue_block_asm(uint4 (&A)[4], const uint8_t *ms
     A[3] = make_uint4(a3[0], a3[1], a3[2], a3[3]);
 }
 
+// kIoToRounds: the next round's three table entries (length, destination
+// offset, source offset) issued from asm ahead of the current round's walk, so
+// that hipcc neither sinks them to their use nor counts them.  They are older
+// than every VMEM op of that walk, so the walk's counted waits hold as they
+// are (an older load in flight can only make a counted wait retire more).
+__device__ __forceinline__ void issue_round_asm(uint32_t &nl, uint64_t &no, uint64_t &ns, const uint32_t *pl,
+                                                const uint64_t *po, const uint64_t *ps)
+{
+    asm volatile(
+        "global_load_dword %[l], %[pl], off\n\t"
+        "global_load_dwordx2 %[o], %[po], off\n\t"
+        "global_load_dwordx2 %[s], %[ps], off\n\t"
+        : [l] "=&v"(nl), [o] "=&v"(no), [s] "=&v"(ns)
+        : [pl] "v"(pl), [po] "v"(po), [ps] "v"(ps)
+        : "memory");
+}
+
+// The wait that retires them, after the walk: vmcnt(0), on every path.  How
+// many VMEM ops a walk issues depends on its lane's length and alignment
+// (none at all for a zero length), so no count is valid for every wave; the
+// price is that the round's last stores are drained here too.
+__device__ __forceinline__ void round_wait_asm(uint32_t &nl, uint64_t &no, uint64_t &ns)
+{
+    asm volatile("s_waitcnt vmcnt(0)" : "+v"(nl), "+v"(no), "+v"(ns) :: "memory");
+}
+
 // The I/O form of a crypt kernel (last template parameter of the window, half-
 // group, whole-group and declared kernels):
 //   kIoInPlace  the span is read, XORed and written back (zrc4_crypt_*);
@@ -644,8 +686,12 @@ __device__ __forceinline__ void issue_block_asm(uint4 (&A)[4], const uint8_t *ms
 //               and never read;
 //   kIoTo       out of place (zrc4_crypt_to_*): entry i reads its SOURCE span
 //               and stores the XOR to its destination span; the destination
-//               is never read and the source never written.
-enum CryptIo : int { kIoInPlace = 0, kIoKs = 1, kIoTo = 2 };
+//               is never read and the source never written;
+//   kIoToRounds kIoTo, `rounds` times in one launch (zrc4_crypt_to_*_rounds;
+//               the lane-per-stream kernels only): the group image is loaded
+//               and stored once, and each lane walks its slot's `rounds`
+//               entries in order (crypt_body).
+enum CryptIo : int { kIoInPlace = 0, kIoKs = 1, kIoTo = 2, kIoToRounds = 3 };
 
 // Crypt one lane's message in place: unaligned head bytes, 64-byte blocks
 // (crypt_blocks_asm), 16-byte chunks, tail bytes.  If `pre` is set, A already
@@ -660,7 +706,8 @@ enum CryptIo : int { kIoInPlace = 0, kIoKs = 1, kIoTo = 2 };
 // aligned, and the whole message goes byte by byte (one byte load, one PRGA
 // step, one byte store): correct at any pair of alignments, about as fast as
 // the head and tail loops, and never a read of the destination.
-template <int IO = kIoInPlace>
+// DRAIN (kIoTo in a rounds kernel): crypt_blocks_to_asm<true>.
+template <int IO = kIoInPlace, bool DRAIN = false>
 __device__ __forceinline__ void crypt_message(uint8_t *S, Rc4Lane &st, uint8_t *msg,
                                               uint32_t len, uint4 (&A)[4], bool pre, uint64_t delta = 0)
 {
@@ -689,7 +736,7 @@ __device__ __forceinline__ void crypt_message(uint8_t *S, Rc4Lane &st, uint8_t *
             keystream_blocks_asm(st, p, nblk);
         } else if constexpr (TO) {
             if (!pre) issue_block_asm(A, reinterpret_cast<const uint8_t *>((uintptr_t)p + delta));
-            crypt_blocks_to_asm(st, p, nblk, A, delta);
+            crypt_blocks_to_asm<DRAIN>(st, p, nblk, A, delta);
         } else {
             if (!pre) issue_block_asm(A, reinterpret_cast<const uint8_t *>(p));
             crypt_blocks_asm(st, p, nblk, A);
@@ -1234,16 +1281,21 @@ struct FrameArgs {
 // pointers in the FrameArgs position of the argument list: the argument
 // layout -- and with it the machine code -- of every other instantiation is
 // what it was before the form existed.
+// kIoToRounds: `rounds` and the tables' round stride (the call's n) sit in
+// what were spare bytes, for the same reason.
 struct ToArgs {
     const uint8_t *src;        // source of entry e = src + src_off[e] ...
     const uint64_t *src_off;   // ... len[e] bytes
-    uint64_t unused[5];
+    uint32_t rounds, stride;   // kIoToRounds: entry e of round r is table index r * stride + e
+    uint64_t unused[4];
 };
 static_assert(sizeof(ToArgs) == sizeof(FrameArgs), "ToArgs stands where FrameArgs does");
 template <int IO>
 struct AuxArgsOf { using type = FrameArgs; };
 template <>
 struct AuxArgsOf<kIoTo> { using type = ToArgs; };
+template <>
+struct AuxArgsOf<kIoToRounds> { using type = ToArgs; };
 template <int IO>
 using AuxArgs = typename AuxArgsOf<IO>::type;
 
@@ -1390,7 +1442,10 @@ crypt_body(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy,
            uint32_t *__restrict__ err, uint8_t *__restrict__ sink, const AuxArgs<IO> &fr, const Claim &cl,
            const BucketGroups *dg = nullptr)
 {
-    constexpr bool KS = IO == kIoKs, TO = IO == kIoTo;
+    // ROUNDS: the out-of-place form with `fr.rounds` entries per slot.  Round
+    // 0's entries are the ones every path below loads (and the only ones the
+    // prologue loads); a bucket is judged busy by its ids alone.
+    constexpr bool KS = IO == kIoKs, ROUNDS = IO == kIoToRounds, TO = IO == kIoTo || ROUNDS;
     static_assert(!HALF || MODE != kIds, "half-group workgroups run range and grouped batches");
     static_assert(!DECL || MODE == kGrouped, "declared groups are a grouped-batch form");
     static_assert(!KS || (!FRAME && MODE != kIds), "write-only keystream: range and grouped batches, never framed");
@@ -1538,7 +1593,7 @@ crypt_body(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy,
                 id = ZRC4_INVALID;
             }
             idq[q] = id;
-            bq[q] = id != ZRC4_INVALID && lq[q] != 0u;
+            bq[q] = id != ZRC4_INVALID && (ROUNDS || lq[q] != 0u);
         }
         // Speculative image (and x/y) issue: the wave's first busy id names
         // the bucket's group, so the image load overlaps the table build.  A
@@ -1628,7 +1683,7 @@ crypt_body(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy,
         if (!DECL && tid == 0 && !have) cold = claim_part(cl, g, HALF ? h : 0u, w);
         if constexpr (DECL) claim_wait(cold);            // (the image too: it is needed by the fill next)
         if (tid == 0) flag[3] = claim_lost(cl, cold) ? 1u : 0u;          // read after the fill barrier
-        if (!mylen) sxy = 0;
+        if (ROUNDS ? ent == ZRC4_INVALID : !mylen) sxy = 0;
         if constexpr (FRAME) {
             // entries that decrypt nothing are framed by their own thread now
             if (valid && !busy)
@@ -1654,7 +1709,8 @@ crypt_body(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy,
         whole = flag[0] != 0u;
         __syncthreads();
     }
-    const bool active = slot != ZRC4_INVALID && mylen != 0u;
+    // (ROUNDS: a lane runs when its slot is named, whatever round 0's length)
+    const bool active = slot != ZRC4_INVALID && (ROUNDS ? ent != ZRC4_INVALID : mylen != 0u);
 
     uint8_t *msg = payload + myoff;
     uint4 A[4];
@@ -1665,16 +1721,23 @@ crypt_body(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy,
     // (KS stores keystream and loads no payload: there is no block 0 to issue;
     // an out-of-place entry whose addresses are not congruent mod 16 goes byte
     // by byte, crypt_message)
-    const bool pre = !KS && active && mylen >= 64u && head_bytes(msg, mylen) == 0u && (!TO || (delta & 15u) == 0u);
+    // (ROUNDS issues every round's lead block inside its walk: ahead of the
+    // fill the block would stay in flight across the code of the other lanes'
+    // heads, pieces and tails, which hipcc gave v40..v47 to; the 64 keystream
+    // bytes ZL_FIRST computes before it needs the block cover the round trip)
+    const bool pre = !KS && !ROUNDS && active && mylen >= 64u && head_bytes(msg, mylen) == 0u &&
+                     (!TO || (delta & 15u) == 0u);
     if constexpr (MODE != kIds) {
         // The image was issued before the entry loads still in flight (kRange:
         // len, off and x/y; kGrouped: x/y).  Waited on every path (the
         // registers must not be reused while it is in flight); the first
         // payload block is issued after this wait, so its round trip overlaps
         // the LDS fill.
-        if constexpr (MODE == kRange)
+        if constexpr (MODE == kRange && !ROUNDS)
             asm volatile("s_waitcnt vmcnt(3)" : "+{v[160:191]}"(ilo), "+{v[192:223]}"(ihi) :: "memory");
-        else   // the x/y load is conditional: wait for everything
+        else   // the x/y load is conditional: wait for everything (ROUNDS: with no lead
+               // block ahead of the fill nothing needs the offsets before this wait, and
+               // hipcc sinks their loads below it: no count of younger loads holds)
             asm volatile("s_waitcnt vmcnt(0)" : "+{v[160:191]}"(ilo), "+{v[192:223]}"(ihi) :: "memory");
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
@@ -1707,7 +1770,35 @@ crypt_body(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy,
     if (active) {
         Rc4Lane st;
         lane_init(st, S, col, sxy);
-        crypt_message<IO>(S, st, msg, mylen, A, pre, delta);
+        if constexpr (ROUNDS) {
+            // Rounds are lane-local: x, y and the S-box column stay where they
+            // are between them, and no barrier is needed.  Each round issues
+            // the next round's entries (issue_round_asm), walks its own, and
+            // only then waits for them; the last round re-reads its own
+            // entries, so that the asm runs on every path.  A zero length
+            // skips the walk.  Round 0 stands apart only in that its entries
+            // came with the prologue's loads.
+            const uint32_t R = fr.rounds;
+            size_t idx = ent;
+            uint32_t nl;
+            uint64_t no, ns;
+            if (R > 1u) idx += fr.stride;
+            issue_round_asm(nl, no, ns, len + idx, off + idx, fr.src_off + idx);
+            if (mylen) crypt_message<kIoTo, true>(S, st, msg, mylen, A, pre, delta);
+            round_wait_asm(nl, no, ns);
+            for (uint32_t r = 1; r < R; ++r) {
+                const uint32_t L = nl;
+                uint8_t *m = payload + no;
+                const uint64_t d = (uint64_t)(uintptr_t)(fr.src + ns) - (uint64_t)(uintptr_t)m;
+                if (r + 1u < R) idx += fr.stride;
+                issue_round_asm(nl, no, ns, len + idx, off + idx, fr.src_off + idx);
+                uint4 B[4];
+                if (L) crypt_message<kIoTo, true>(S, st, m, L, B, false, d);
+                round_wait_asm(nl, no, ns);
+            }
+        } else {
+            crypt_message<IO>(S, st, msg, mylen, A, pre, delta);
+        }
         xy[slot] = lane_xy(st);
     }
     if constexpr (FRAME) {
