@@ -32,9 +32,11 @@ FRAME_DEPS = FRAME_SOURCES + [ROOT / "include" / "zsummerx_amd" / "frame.h",
                               ROOT / "include" / "zsummerx_amd" / "rc4_hooks.h", ROOT / "include" / "zrc4.h"]
 ROCM = Path(os.environ.get("ROCM_PATH", "/opt/rocm"))
 
-HIP_SOURCES = [CSRC / "zrc4.hip"]
-HIP_DEPS = HIP_SOURCES + [CSRC / "zrc4_kernels.hpp", CSRC / "zrc4_win.hpp", CSRC / "zrc4_line_loop.inc", CSRC / "zrc4_ks.inc",
-                         ROOT / "include" / "zrc4.h"]
+# Everything under csrc/ that libzrc4.so is compiled from: the translation unit
+# first, then what it includes.
+HIP_CSRC = ("zrc4.hip", "zrc4_plan.hpp", "zrc4_kernels.hpp", "zrc4_win.hpp", "zrc4_line_loop.inc", "zrc4_ks.inc")
+HIP_SOURCES = [CSRC / HIP_CSRC[0]]
+HIP_DEPS = [CSRC / f for f in HIP_CSRC] + [ROOT / "include" / "zrc4.h"]
 
 
 def _hipcc() -> str:
@@ -87,22 +89,19 @@ def build_variant(name: str, defines: dict, rev: str | None = None) -> Path:
         tree = BUILD / f"rev_{name}"
         (tree / "csrc").mkdir(parents=True, exist_ok=True)
         (tree / "include").mkdir(parents=True, exist_ok=True)
-        for rel, dst in (("zsummerx_amd/csrc/zrc4.hip", tree / "csrc" / "zrc4.hip"),
-                         ("zsummerx_amd/csrc/zrc4_kernels.hpp", tree / "csrc" / "zrc4_kernels.hpp"),
-                         ("zsummerx_amd/csrc/zrc4_win.hpp", tree / "csrc" / "zrc4_win.hpp"),
-                         ("zsummerx_amd/csrc/zrc4_line_loop.inc", tree / "csrc" / "zrc4_line_loop.inc"),
-                         ("zsummerx_amd/csrc/zrc4_ks.inc", tree / "csrc" / "zrc4_ks.inc"),
-                         ("include/zrc4.h", tree / "include" / "zrc4.h")):
+        for rel, dst in [(f"zsummerx_amd/csrc/{f}", tree / "csrc" / f) for f in HIP_CSRC] + \
+                        [("include/zrc4.h", tree / "include" / "zrc4.h")]:
             got = subprocess.run(["git", "show", f"{rev}:{rel}"], cwd=ROOT, capture_output=True)
             if got.returncode != 0:
-                if rel.endswith((".inc", "zrc4_win.hpp")):   # older revisions lack these
+                if dst.name not in ("zrc4.hip", "zrc4_kernels.hpp", "zrc4.h"):   # older revisions lack the others
+                    dst.unlink(missing_ok=True)
                     continue
                 got.check_returncode()
             blob = got.stdout
             if not dst.exists() or dst.read_bytes() != blob:
                 dst.write_bytes(blob)
         srcs, inc = [tree / "csrc" / "zrc4.hip"], tree / "include"
-        deps = [tree / "csrc" / "zrc4.hip", tree / "csrc" / "zrc4_kernels.hpp", inc / "zrc4.h"]
+        deps = [p for p in (tree / "csrc" / f for f in HIP_CSRC) if p.exists()] + [inc / "zrc4.h"]
     if _stale(out, deps):
         BUILD.mkdir(exist_ok=True)
         cmd = [_hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-shared",
@@ -158,8 +157,11 @@ def build_test_tools(force: bool = False, sanitize: bool | str = False) -> Path:
       tools/bin/emu_keystream_check the emulated write-only keystream calls
                                  (tests/cpp/emu_zrc4_keystream.cpp) against
                                  the oracle and the header's rules
-    sanitize=True builds only the two emulated binaries, with ASan + UBSan,
-    into tools/bin/san/ (scripts/sanitize.sh runs the CPU suites on them);
+      tools/bin/plan_check       csrc/zrc4_plan.hpp alone (g++, no HIP): the
+                                 kernel choice against a hand-written table,
+                                 and the plans of a shape sweep as text
+    sanitize=True builds only the two emulated binaries and plan_check, with
+    ASan + UBSan, into tools/bin/san/ (scripts/sanitize.sh runs the CPU suites on them);
     sanitize="thread" the same with ThreadSanitizer into tools/bin/tsan/ (the
     reservoir's XOR worker threads)."""
     frame = build_frame(force)
@@ -172,6 +174,7 @@ def build_test_tools(force: bool = False, sanitize: bool | str = False) -> Path:
     emu_ks = ROOT / "tests" / "cpp" / "emu_zrc4_keystream.cpp"    # zrc4_keystream_* over emu's public ABI
     ks_chk = ROOT / "tests" / "cpp" / "emu_keystream_check.cpp"
     dev = ENGINE / "rc4_hooks_device.cpp"
+    plan_chk = ROOT / "tests" / "cpp" / "plan_check.cpp"
     common = ["-std=c++17", f"-I{ROOT / 'include'}", f"-I{ROOT / 'oracle'}"]
     emu_flags = ["-D__HIP_PLATFORM_AMD__", f"-I{ROCM / 'include'}"]
     oracle_link = [f"-L{ROOT / 'oracle'}", "-loracle", "-Wl,-rpath,$ORIGIN/../../oracle"]
@@ -193,10 +196,16 @@ def build_test_tools(force: bool = False, sanitize: bool | str = False) -> Path:
          ["g++", "-O2", *common, *emu_flags, "-o", str(out / "frame_stress_emu"), str(ROOT / "tools" / "frame_stress.cpp"),
           *map(str, FRAME_SOURCES), str(emu), str(emu_ks), *oracle_link, "-ldl", "-lpthread"]),
     ]
+    # (an older tests/ tree run against this build has no plan_check.cpp and
+    # no test that asks for the binary: then there is nothing to build)
+    if plan_chk.exists():
+        jobs.append((out / "plan_check", [plan_chk, CSRC / "zrc4_plan.hpp"],
+                     ["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", f"-I{CSRC}", "-o", str(out / "plan_check"),
+                      str(plan_chk)]))
     if sanitize:
         flags = TSAN if sanitize == "thread" else SANITIZE
         jobs = [(t, d, [c[0], *flags, *c[1:], "-Wl,-rpath,$ORIGIN/../../../oracle"])
-                for t, d, c in jobs if t.name.endswith("_emu")]
+                for t, d, c in jobs if t.name.endswith("_emu") or (t.name == "plan_check" and sanitize is True)]
     for target, deps, cmd in jobs:
         if force or _stale(target, deps):
             subprocess.run(cmd, check=True)

@@ -4,6 +4,7 @@
 // The device arena replaces the by-value RC4Encryption members of TcpSession
 // (include/zsummerX/frame/session.h:115-116); see INTEGRATION.md.
 #include "zrc4.h"
+#include "zrc4_plan.hpp"
 #include "zrc4_kernels.hpp"
 #include "zrc4_win.hpp"
 
@@ -14,6 +15,7 @@
 #include <algorithm>
 #include <vector>
 #include <new>
+#include <type_traits>
 #include <thread>
 
 struct zrc4_ctx {
@@ -96,324 +98,272 @@ size_t align16(size_t v) { return (v + 15u) & ~(size_t)15u; }
 
 constexpr size_t kZeroCopyMax = 256u << 10;   // *_host batches up to this size run on pinned staging in place
 
-// Kernel choice per launch: more 256-slot groups than CUs -> the persistent
-// throughput kernel (2 workgroups per CU, whole-line stores through the DPP
-// transpose); otherwise one group per workgroup (crypt_kernel: chain-bound,
-// per-lane stores).  A/B: the DPP path is 5-7 us slower at one group per CU
-// (cfg2 56.1 vs 48.8 us, cfg3 28.1 vs 22.7 us; profiles/r02_ab_dpp_direct.log).
-// With `fr`, the framing walk of every entry runs in the same launch: in the
-// direct kernels' epilogue, or in the persistent kernel's tail.
-//
-// `decl` (kGrouped only): the caller's declared group per 256-entry bucket, in
-// host memory (zrc4_crypt_grouped_declared).  Window launches take it in the
-// kernel arguments (the image leaves at kernel entry); larger launches check
-// it first in decl_check_kernel, which blocks the groups of a disagreeing
-// bucket through the claims.  `decl_trusted`: the groups were computed here
-// from host ids (zrc4_crypt_host), so larger launches skip the check.
-//
-// `io` = zrc4::kIoKs (kRange / kGrouped, never with `fr`): write-only keystream
-// (zrc4_keystream_*): every entry's span receives its slot's next len bytes of
-// keystream and is never read.  The window, half- and whole-group kernels have
-// a KS form of their own; the persistent kernel has none, so there the spans
-// are zeroed first by span_fill_kernel on the same stream (0 ^ k = k).
-//
-// `io` = zrc4::kIoTo with `src` / `src_off` (zrc4_crypt_to_*; the same
-// restrictions as `ks`): entry i reads src + src_off[i] and stores to payload
-// + off[i].  Again the window, half- and whole-group kernels have the form;
-// ahead of the persistent kernel span_copy_kernel copies the sources into the
-// destinations on the same stream, and the in-place launch runs over those.
-//
-// `io` = zrc4::kIoToRounds with `rounds` >= 2 (zrc4_crypt_to_*_rounds): off,
-// len and src_off hold rounds * n entries, round-major, and every slot runs
-// its `rounds` entries in order in ONE launch of the half-group, whole-group
-// or declared kernel -- also at 32 groups and fewer: the window kernel has no
-// rounds form.  With more groups than CUs the rounds are `rounds` successive
-// kIoTo calls on the stream, from the loop below.
-int launch_crypt(zrc4_ctx *c, int mode, const uint32_t *ids, uint32_t first_slot, uint8_t *payload,
-                 const uint64_t *off, const uint32_t *len, uint32_t n, hipStream_t s,
-                 const zrc4::FrameArgs *fr = nullptr, const uint32_t *decl = nullptr, bool decl_trusted = false,
-                 int io = zrc4::kIoInPlace, const uint8_t *src = nullptr, const uint64_t *src_off = nullptr,
-                 uint32_t rounds = 1)
+int launched() { return hipGetLastError() == hipSuccess ? ZRC4_OK : ZRC4_ERR_LAUNCH; }
+
+// One crypt, keystream or out-of-place call, as launch_crypt takes it.
+struct CryptCall {
+    int mode = zrc4::kRange;            // zrc4::CryptMode
+    const uint32_t *ids = nullptr;
+    uint32_t first_slot = 0;
+    uint8_t *payload = nullptr;         // kIoKs / kIoTo / kIoToRounds: the destination
+    const uint64_t *off = nullptr;
+    const uint32_t *len = nullptr;
+    uint32_t n = 0;
+    const zrc4::FrameArgs *frame = nullptr;   // the framing walk of every entry runs in the same launch
+    const uint32_t *decl = nullptr;     // kGrouped: the declared group per 256-entry bucket, in host memory
+    bool trusted = false;               // ... computed here from host ids (zrc4_crypt_host, the reservoirs)
+    int io = zrc4::kIoInPlace;          // zrc4::CryptIo
+    const uint8_t *src = nullptr;       // kIoTo / kIoToRounds: entry i reads src + src_off[i]
+    const uint64_t *src_off = nullptr;
+    uint32_t rounds = 1;                // kIoToRounds: off, len and src_off hold rounds * n entries, round-major
+};
+
+// The arguments every call has, in the public entry points' order; a caller
+// sets the others by name.
+CryptCall crypt_call(int mode, const uint32_t *ids, uint32_t first_slot, uint8_t *payload, const uint64_t *off,
+                     const uint32_t *len, uint32_t n)
 {
-    if (n == 0) return ZRC4_OK;
-    const bool ks = io == zrc4::kIoKs, to = io == zrc4::kIoTo, tor = io == zrc4::kIoToRounds;
-    if ((ks || to || tor) && (fr || mode == zrc4::kIds)) return ZRC4_ERR_INVALID_ARG;
-    if ((to || tor) && (!src || !src_off)) return ZRC4_ERR_INVALID_ARG;
-    if (tor && (rounds < 2u || (uint64_t)n * rounds > 0xFFF00000u)) return ZRC4_ERR_INVALID_ARG;
-    zrc4::ToArgs ta{};
-    ta.src = src;
-    ta.src_off = src_off;
-    ta.rounds = rounds;
-    ta.stride = n;
-    if (mode == zrc4::kRange && (uint64_t)first_slot + n > c->capacity) return ZRC4_ERR_SLOT_RANGE;
-    if (tor && (n + zrc4::kGroup - 1) / zrc4::kGroup > (uint32_t)c->num_cus) {
-        // the persistent kernel has no out-of-place form, so no rounds form
-        // either: one two-launch kIoTo sequence per round (claims per round)
-        for (uint32_t r = 0; r < rounds; ++r) {
-            const size_t at = (size_t)r * n;
-            const int rc = launch_crypt(c, mode, ids, first_slot, payload, off + at, len + at, n, s, nullptr, decl,
-                                        decl_trusted, zrc4::kIoTo, src, src_off + at);
-            if (rc != ZRC4_OK) return rc;
-        }
-        return ZRC4_OK;
-    }
-    zrc4::Claim cl{nullptr, 0u, nullptr};
-    if (mode == zrc4::kGrouped) {
-        // a fresh tag per grouped launch; on the 32-bit wrap the words are
-        // zeroed first (stream-ordered before this launch)
-        if (++c->epoch == 0u) {
-            ZRC4_TRY(hipMemsetAsync(c->claim, 0, (size_t)(c->capacity / zrc4::kGroup) * zrc4::kClaimParts * 8u, s));
-            c->epoch = 1u;
-        }
-        cl = zrc4::Claim{c->claim, c->epoch,
-                         reinterpret_cast<const uint32_t *>(c->claim + (size_t)(c->capacity / zrc4::kGroup) * zrc4::kClaimParts)};
-    }
-    const uint32_t grid = (n + zrc4::kGroup - 1) / zrc4::kGroup;
-    const dim3 blk(zrc4::kGroup);
-    const bool stream_kernel = grid > (uint32_t)c->num_cus;
-    // (the grouped stream kernel computes entry indexes of the bucket after
-    // next in 32 bits)
-    if (mode == zrc4::kGrouped && stream_kernel && n > 0xFFF00000u) return ZRC4_ERR_INVALID_ARG;
-    // Few aligned groups (at most kWinMaxBuckets, so that declared groups
-    // travel in WinGroups): 16 lanes per stream (speculative windows,
-    // crypt_win_kernel), one wave per 4 streams, 64 workgroups per group.
-    if (!tor && grid <= zrc4::kWinMaxBuckets &&
-        ((mode == zrc4::kRange && (first_slot & 255u) == 0u) || mode == zrc4::kGrouped)) {
-        const dim3 wgrid(64u * grid), wblk(64);
-        const zrc4::FrameArgs fa = fr ? *fr : zrc4::FrameArgs{};
-        zrc4::WinGroups dg{};
-        if (decl && mode == zrc4::kGrouped)
-            for (uint32_t b = 0; b < grid; ++b) dg.g[b] = decl[b];
-#define ZRC4_WIN_(MODE_, FRAME_, DECL_, IO_, AUX_)                                                             \
-    hipLaunchKernelGGL((zrc4::crypt_win_kernel<MODE_, FRAME_, DECL_, IO_>), wgrid, wblk, 0, s, c->arena, c->xy, \
-                       ids, first_slot, payload, off, len, n, c->capacity, c->err, c->sink, AUX_, cl, dg)
-#define ZRC4_WIN(MODE_, FRAME_, DECL_, IO_) ZRC4_WIN_(MODE_, FRAME_, DECL_, IO_, fa)
-        if (to && mode == zrc4::kRange)
-            ZRC4_WIN_(zrc4::kRange, false, false, zrc4::kIoTo, ta);
-        else if (to && decl)
-            ZRC4_WIN_(zrc4::kGrouped, false, true, zrc4::kIoTo, ta);
-        else if (to)
-            ZRC4_WIN_(zrc4::kGrouped, false, false, zrc4::kIoTo, ta);
-        else if (ks && mode == zrc4::kRange)
-            ZRC4_WIN(zrc4::kRange, false, false, zrc4::kIoKs);
-        else if (ks && decl)
-            ZRC4_WIN(zrc4::kGrouped, false, true, zrc4::kIoKs);
-        else if (ks)
-            ZRC4_WIN(zrc4::kGrouped, false, false, zrc4::kIoKs);
-        else if (mode == zrc4::kRange && fr)
-            ZRC4_WIN(zrc4::kRange, true, false, zrc4::kIoInPlace);
-        else if (mode == zrc4::kRange)
-            ZRC4_WIN(zrc4::kRange, false, false, zrc4::kIoInPlace);
-        else if (decl && fr)
-            ZRC4_WIN(zrc4::kGrouped, true, true, zrc4::kIoInPlace);
-        else if (decl)
-            ZRC4_WIN(zrc4::kGrouped, false, true, zrc4::kIoInPlace);
-        else if (fr)
-            ZRC4_WIN(zrc4::kGrouped, true, false, zrc4::kIoInPlace);
-        else
-            ZRC4_WIN(zrc4::kGrouped, false, false, zrc4::kIoInPlace);
-#undef ZRC4_WIN
-#undef ZRC4_WIN_
-        return hipGetLastError() == hipSuccess ? ZRC4_OK : ZRC4_ERR_LAUNCH;
-    }
-    // Declared groups on the half-group / whole-group kernels (at most 256
-    // buckets, one bucket per CU): in the kernel arguments, checked there.
-    if (decl && mode == zrc4::kGrouped && !stream_kernel && grid <= zrc4::kBodyMaxBuckets) {
-        zrc4::BucketGroups dg{};
-        for (uint32_t b = 0; b < grid; ++b) dg.g[b] = decl[b];
-        const zrc4::FrameArgs fa = fr ? *fr : zrc4::FrameArgs{};
-        const bool half = 2u * grid <= (uint32_t)c->num_cus;
-#define ZRC4_DECL_(FRAME_, HALF_, IO_, GRID_, BLK_, AUX_)                                                   \
-    hipLaunchKernelGGL((zrc4::crypt_decl_kernel<FRAME_, HALF_, IO_>), GRID_, BLK_, 0, s, c->arena, c->xy, ids, \
-                       payload, off, len, n, c->capacity, c->err, c->sink, AUX_, cl, dg)
-#define ZRC4_DECL(FRAME_, HALF_, IO_, GRID_, BLK_) ZRC4_DECL_(FRAME_, HALF_, IO_, GRID_, BLK_, fa)
-        if (half && tor)
-            ZRC4_DECL_(false, true, zrc4::kIoToRounds, dim3(2u * grid), dim3(zrc4::kHalfBlock), ta);
-        else if (tor)
-            ZRC4_DECL_(false, false, zrc4::kIoToRounds, dim3(grid), blk, ta);
-        else if (half && to)
-            ZRC4_DECL_(false, true, zrc4::kIoTo, dim3(2u * grid), dim3(zrc4::kHalfBlock), ta);
-        else if (to)
-            ZRC4_DECL_(false, false, zrc4::kIoTo, dim3(grid), blk, ta);
-        else if (half && ks)
-            ZRC4_DECL(false, true, zrc4::kIoKs, dim3(2u * grid), dim3(zrc4::kHalfBlock));
-        else if (ks)
-            ZRC4_DECL(false, false, zrc4::kIoKs, dim3(grid), blk);
-        else if (half && fr)
-            ZRC4_DECL(true, true, zrc4::kIoInPlace, dim3(2u * grid), dim3(zrc4::kHalfBlock));
-        else if (half)
-            ZRC4_DECL(false, true, zrc4::kIoInPlace, dim3(2u * grid), dim3(zrc4::kHalfBlock));
-        else if (fr)
-            ZRC4_DECL(true, false, zrc4::kIoInPlace, dim3(grid), blk);
-        else
-            ZRC4_DECL(false, false, zrc4::kIoInPlace, dim3(grid), blk);
-#undef ZRC4_DECL
-#undef ZRC4_DECL_
-        return hipGetLastError() == hipSuccess ? ZRC4_OK : ZRC4_ERR_LAUNCH;
-    }
-    if (decl && mode == zrc4::kGrouped && !decl_trusted) {
-        // check the declared groups before the crypt launch (stream-ordered):
-        // a disagreeing bucket's groups are claimed under this launch's epoch
-        const int k = (int)(c->decl_next++ % (uint32_t)zrc4_ctx::kDeclRing);
-        if (c->decl_ev_live[k]) ZRC4_TRY(hipEventSynchronize(c->decl_ev[k]));    // its last reader has run
-        if (!c->decl_ev[k] && hipEventCreateWithFlags(&c->decl_ev[k], hipEventDisableTiming) != hipSuccess)
-            return ZRC4_ERR_HIP;
-        if (grid > c->h_decl_cap[k]) {
-            if (c->h_decl[k]) (void)hipHostFree(c->h_decl[k]);
-            c->h_decl[k] = nullptr;
-            c->h_decl_cap[k] = 0;
-            uint32_t want = 1024u;
-            while (want < grid) want <<= 1;
-            void *p = nullptr;
-            if (hipHostMalloc(&p, (size_t)want * 4u, hipHostMallocCoherent) != hipSuccess) return ZRC4_ERR_OUT_OF_MEMORY;
-            c->h_decl[k] = static_cast<uint32_t *>(p);
-            c->h_decl_cap[k] = want;
-        }
-        memcpy(c->h_decl[k], decl, (size_t)grid * 4u);
-        hipLaunchKernelGGL(zrc4::decl_check_kernel, dim3(grid), blk, 0, s, ids, len, n, c->h_decl[k], c->capacity,
-                           cl, c->err);
-        if (hipGetLastError() != hipSuccess) return ZRC4_ERR_LAUNCH;
-        ZRC4_TRY(hipEventRecord(c->decl_ev[k], s));
-        c->decl_ev_live[k] = true;
-    }
-    // Few whole groups: half-group workgroups, one per CU (2 waves per CU).
-    // A grouped bucket's slots may sit in either half whatever its entry
-    // count, so it always gets both halves.
-    const bool half = 2u * grid <= (uint32_t)c->num_cus &&
-                      ((mode == zrc4::kRange && (first_slot & 255u) == 0u) || mode == zrc4::kGrouped);
-    if (half) {
-        const dim3 hblk(zrc4::kHalfBlock);
-        const dim3 hgrid(mode == zrc4::kGrouped ? 2u * grid : (n + zrc4::kGroup / 2 - 1) / (zrc4::kGroup / 2));
-        const zrc4::FrameArgs fa = fr ? *fr : zrc4::FrameArgs{};
-        if (tor && mode == zrc4::kRange)
-            hipLaunchKernelGGL((zrc4::crypt_half_kernel<zrc4::kRange, false, zrc4::kIoToRounds>), hgrid, hblk, 0, s,
-                               c->arena, c->xy, ids, first_slot, payload, off, len, n, c->capacity, c->err, c->sink, ta);
-        else if (tor)
-            hipLaunchKernelGGL((zrc4::crypt_half_kernel<zrc4::kGrouped, false, zrc4::kIoToRounds>), hgrid, hblk, 0, s,
-                               c->arena, c->xy, ids, first_slot, payload, off, len, n, c->capacity, c->err, c->sink, ta,
-                               cl);
-        else if (to && mode == zrc4::kRange)
-            hipLaunchKernelGGL((zrc4::crypt_half_kernel<zrc4::kRange, false, zrc4::kIoTo>), hgrid, hblk, 0, s, c->arena,
-                               c->xy, ids, first_slot, payload, off, len, n, c->capacity, c->err, c->sink, ta);
-        else if (to)
-            hipLaunchKernelGGL((zrc4::crypt_half_kernel<zrc4::kGrouped, false, zrc4::kIoTo>), hgrid, hblk, 0, s,
-                               c->arena, c->xy, ids, first_slot, payload, off, len, n, c->capacity, c->err, c->sink, ta,
-                               cl);
-        else if (ks && mode == zrc4::kRange)
-            hipLaunchKernelGGL((zrc4::crypt_half_kernel<zrc4::kRange, false, zrc4::kIoKs>), hgrid, hblk, 0, s, c->arena,
-                               c->xy, ids, first_slot, payload, off, len, n, c->capacity, c->err, c->sink, fa);
-        else if (ks)
-            hipLaunchKernelGGL((zrc4::crypt_half_kernel<zrc4::kGrouped, false, zrc4::kIoKs>), hgrid, hblk, 0, s,
-                               c->arena, c->xy, ids, first_slot, payload, off, len, n, c->capacity, c->err, c->sink, fa,
-                               cl);
-        else if (mode == zrc4::kRange) {
-            if (fr)
-                hipLaunchKernelGGL((zrc4::crypt_half_kernel<zrc4::kRange, true>), hgrid, hblk, 0, s, c->arena, c->xy,
-                                   ids, first_slot, payload, off, len, n, c->capacity, c->err, c->sink, fa);
-            else
-                hipLaunchKernelGGL((zrc4::crypt_half_kernel<zrc4::kRange, false>), hgrid, hblk, 0, s, c->arena, c->xy,
-                                   ids, first_slot, payload, off, len, n, c->capacity, c->err, c->sink, fa);
-        } else {
-            if (fr)
-                hipLaunchKernelGGL((zrc4::crypt_half_kernel<zrc4::kGrouped, true>), hgrid, hblk, 0, s, c->arena,
-                                   c->xy, ids, first_slot, payload, off, len, n, c->capacity, c->err, c->sink, fa, cl);
-            else
-                hipLaunchKernelGGL((zrc4::crypt_half_kernel<zrc4::kGrouped, false>), hgrid, hblk, 0, s, c->arena,
-                                   c->xy, ids, first_slot, payload, off, len, n, c->capacity, c->err, c->sink, fa, cl);
-        }
-        return hipGetLastError() == hipSuccess ? ZRC4_OK : ZRC4_ERR_LAUNCH;
-    }
-    if (fr && !stream_kernel) {
-        if (mode == zrc4::kRange)
-            hipLaunchKernelGGL((zrc4::crypt_kernel<zrc4::kRange, true>), dim3(grid), blk, 0, s, c->arena, c->xy,
-                               ids, first_slot, payload, off, len, n, c->capacity, c->err, c->sink, *fr);
-        else if (mode == zrc4::kGrouped)
-            hipLaunchKernelGGL((zrc4::crypt_kernel<zrc4::kGrouped, true>), dim3(grid), blk, 0, s, c->arena, c->xy,
-                               ids, first_slot, payload, off, len, n, c->capacity, c->err, c->sink, *fr, cl);
-        else
-            return ZRC4_ERR_INVALID_ARG;
-        return hipGetLastError() == hipSuccess ? ZRC4_OK : ZRC4_ERR_LAUNCH;
-    }
-    if (ks && !stream_kernel) {
-        if (mode == zrc4::kRange)
-            hipLaunchKernelGGL((zrc4::crypt_kernel<zrc4::kRange, false, zrc4::kIoKs>), dim3(grid), blk, 0, s, c->arena,
-                               c->xy, ids, first_slot, payload, off, len, n, c->capacity, c->err, c->sink);
-        else
-            hipLaunchKernelGGL((zrc4::crypt_kernel<zrc4::kGrouped, false, zrc4::kIoKs>), dim3(grid), blk, 0, s,
-                               c->arena, c->xy, ids, first_slot, payload, off, len, n, c->capacity, c->err, c->sink,
-                               zrc4::FrameArgs{}, cl);
-        return hipGetLastError() == hipSuccess ? ZRC4_OK : ZRC4_ERR_LAUNCH;
-    }
-    if (tor) {                                           // (never the persistent kernel: handled above)
-        if (mode == zrc4::kRange)
-            hipLaunchKernelGGL((zrc4::crypt_kernel<zrc4::kRange, false, zrc4::kIoToRounds>), dim3(grid), blk, 0, s,
-                               c->arena, c->xy, ids, first_slot, payload, off, len, n, c->capacity, c->err, c->sink, ta);
-        else
-            hipLaunchKernelGGL((zrc4::crypt_kernel<zrc4::kGrouped, false, zrc4::kIoToRounds>), dim3(grid), blk, 0, s,
-                               c->arena, c->xy, ids, first_slot, payload, off, len, n, c->capacity, c->err, c->sink, ta,
-                               cl);
-        return hipGetLastError() == hipSuccess ? ZRC4_OK : ZRC4_ERR_LAUNCH;
-    }
-    if (to && !stream_kernel) {
-        if (mode == zrc4::kRange)
-            hipLaunchKernelGGL((zrc4::crypt_kernel<zrc4::kRange, false, zrc4::kIoTo>), dim3(grid), blk, 0, s, c->arena,
-                               c->xy, ids, first_slot, payload, off, len, n, c->capacity, c->err, c->sink, ta);
-        else
-            hipLaunchKernelGGL((zrc4::crypt_kernel<zrc4::kGrouped, false, zrc4::kIoTo>), dim3(grid), blk, 0, s,
-                               c->arena, c->xy, ids, first_slot, payload, off, len, n, c->capacity, c->err, c->sink, ta,
-                               cl);
-        return hipGetLastError() == hipSuccess ? ZRC4_OK : ZRC4_ERR_LAUNCH;
-    }
-    if (stream_kernel) {
-        if (ks) {
-            // no write-only form of the persistent kernel: zero the spans it
-            // will crypt (one wave per entry, a few waves per SIMD at most)
-            const uint32_t fgrid = (uint32_t)std::min<uint64_t>(((uint64_t)n + 3u) / 4u, 16u * (uint64_t)c->num_cus);
-            hipLaunchKernelGGL(zrc4::span_fill_kernel, dim3(fgrid), blk, 0, s, mode == zrc4::kGrouped ? ids : nullptr,
-                               payload, off, len, n, c->capacity);
-            if (hipGetLastError() != hipSuccess) return ZRC4_ERR_LAUNCH;
-        }
-        if (to) {
-            // no out-of-place form of the persistent kernel: copy the sources
-            // of the entries it will crypt into their destinations
-            const uint32_t fgrid = (uint32_t)std::min<uint64_t>(((uint64_t)n + 3u) / 4u, 16u * (uint64_t)c->num_cus);
-            hipLaunchKernelGGL(zrc4::span_copy_kernel, dim3(fgrid), blk, 0, s, mode == zrc4::kGrouped ? ids : nullptr,
-                               src, src_off, payload, off, len, n, c->capacity);
-            if (hipGetLastError() != hipSuccess) return ZRC4_ERR_LAUNCH;
-        }
-        // with `fr`, the framing walk runs in the same launch, in each
-        // workgroup's tail over the chunks it decrypted (frame_walk_chunks)
-        const uint32_t wgs = std::min(grid, 2u * (uint32_t)c->num_cus);
-        const zrc4::FrameArgs fa = fr ? *fr : zrc4::FrameArgs{};
-#define ZRC4_STREAM(PF_, GR_)                                                                                   \
-    do {                                                                                                       \
-        if (fr)                                                                                                \
-            hipLaunchKernelGGL((zrc4::crypt_stream_kernel<PF_, GR_, true>), dim3(wgs), blk, 0, s, c->arena,    \
-                               c->xy, ids, first_slot, payload, off, len, n, c->capacity, c->err, c->sink, cl, \
-                               fa);                                                                            \
-        else                                                                                                   \
-            hipLaunchKernelGGL((zrc4::crypt_stream_kernel<PF_, GR_, false>), dim3(wgs), blk, 0, s, c->arena,   \
-                               c->xy, ids, first_slot, payload, off, len, n, c->capacity, c->err, c->sink, cl, \
-                               fa);                                                                            \
-    } while (0)
-        if (mode == zrc4::kGrouped)
-            ZRC4_STREAM(true, true);
-        else if (mode == zrc4::kRange && (first_slot & 255u) == 0u)
-            ZRC4_STREAM(true, false);
-        else
-            ZRC4_STREAM(false, false);
-#undef ZRC4_STREAM
-    } else if (mode == zrc4::kRange) {
-        hipLaunchKernelGGL(zrc4::crypt_kernel<zrc4::kRange>, dim3(grid), blk, 0, s, c->arena, c->xy, ids,
-                           first_slot, payload, off, len, n, c->capacity, c->err, c->sink);
-    } else if (mode == zrc4::kGrouped) {
-        hipLaunchKernelGGL(zrc4::crypt_kernel<zrc4::kGrouped>, dim3(grid), blk, 0, s, c->arena, c->xy, ids,
-                           first_slot, payload, off, len, n, c->capacity, c->err, c->sink, zrc4::FrameArgs{}, cl);
+    CryptCall k;
+    k.mode = mode;
+    k.ids = ids;
+    k.first_slot = first_slot;
+    k.payload = payload;
+    k.off = off;
+    k.len = len;
+    k.n = n;
+    return k;
+}
+
+// A runtime value out of a closed list, and with_constants: f(constants...)
+// with every value replaced by the std::integral_constant it equals (f is not
+// called if one of them is outside its list).
+template <typename T, T... Vs>
+struct OneOf {
+    T v;
+};
+using ModeOf = OneOf<int, zrc4::kIds, zrc4::kRange, zrc4::kGrouped>;
+using IoOf = OneOf<int, zrc4::kIoInPlace, zrc4::kIoKs, zrc4::kIoTo, zrc4::kIoToRounds>;
+using BoolOf = OneOf<bool, false, true>;
+
+template <typename F>
+void with_constants(F &&f)
+{
+    f();
+}
+template <typename F, typename T, T... Vs, typename... Rest>
+void with_constants(F &&f, OneOf<T, Vs...> head, Rest... rest)
+{
+    (void)((head.v == Vs &&
+            (with_constants([&](auto... cs) { f(std::integral_constant<T, Vs>{}, cs...); }, rest...), true)) ||
+           ...);
+}
+
+// What a kernel of form IO takes in its FrameArgs position.
+template <int IO>
+zrc4::AuxArgs<IO> aux_args(const CryptCall &k)
+{
+    if constexpr (std::is_same_v<zrc4::AuxArgs<IO>, zrc4::ToArgs>) {
+        zrc4::ToArgs ta{};
+        ta.src = k.src;
+        ta.src_off = k.src_off;
+        ta.rounds = k.rounds;
+        ta.stride = k.n;
+        return ta;
     } else {
-        hipLaunchKernelGGL(zrc4::crypt_kernel<zrc4::kIds>, dim3(grid), blk, 0, s, c->arena, c->xy, ids,
-                           first_slot, payload, off, len, n, c->capacity, c->err, c->sink);
+        return k.frame ? *k.frame : zrc4::FrameArgs{};
     }
-    return hipGetLastError() == hipSuccess ? ZRC4_OK : ZRC4_ERR_LAUNCH;
+}
+
+// The five kernel families, one launch site each.  A launch exists only for
+// the forms zrc4_plan.hpp's predicates name; a plan outside them (there is
+// none) is ZRC4_ERR_INTERNAL.
+int launch_win(zrc4_ctx *c, const CryptCall &k, const zrc4::CryptPlan &p, const zrc4::Claim &cl, hipStream_t s)
+{
+    zrc4::WinGroups dg{};
+    if (p.decl)
+        for (uint32_t b = 0; b < p.groups; ++b) dg.g[b] = k.decl[b];
+    bool hit = false;
+    with_constants(
+        [&](auto M, auto F, auto D, auto IO) {
+            if constexpr (zrc4::win_form_exists(M, F, D, IO)) {
+                hipLaunchKernelGGL((zrc4::crypt_win_kernel<M, F, D, IO>), dim3(p.grid), dim3(p.block), 0, s, c->arena,
+                                   c->xy, k.ids, k.first_slot, k.payload, k.off, k.len, k.n, c->capacity, c->err,
+                                   c->sink, aux_args<IO>(k), cl, dg);
+                hit = true;
+            }
+        },
+        ModeOf{p.mode}, BoolOf{p.frame}, BoolOf{p.decl}, IoOf{p.io});
+    return hit ? launched() : ZRC4_ERR_INTERNAL;
+}
+
+int launch_decl(zrc4_ctx *c, const CryptCall &k, const zrc4::CryptPlan &p, const zrc4::Claim &cl, hipStream_t s)
+{
+    zrc4::BucketGroups dg{};
+    for (uint32_t b = 0; b < p.groups; ++b) dg.g[b] = k.decl[b];
+    bool hit = false;
+    with_constants(
+        [&](auto F, auto H, auto IO) {
+            if constexpr (zrc4::decl_form_exists(F, H, IO)) {
+                hipLaunchKernelGGL((zrc4::crypt_decl_kernel<F, H, IO>), dim3(p.grid), dim3(p.block), 0, s, c->arena,
+                                   c->xy, k.ids, k.payload, k.off, k.len, k.n, c->capacity, c->err, c->sink,
+                                   aux_args<IO>(k), cl, dg);
+                hit = true;
+            }
+        },
+        BoolOf{p.frame}, BoolOf{p.half}, IoOf{p.io});
+    return hit ? launched() : ZRC4_ERR_INTERNAL;
+}
+
+int launch_half(zrc4_ctx *c, const CryptCall &k, const zrc4::CryptPlan &p, const zrc4::Claim &cl, hipStream_t s)
+{
+    bool hit = false;
+    with_constants(
+        [&](auto M, auto F, auto IO) {
+            if constexpr (zrc4::half_form_exists(M, F, IO)) {
+                hipLaunchKernelGGL((zrc4::crypt_half_kernel<M, F, IO>), dim3(p.grid), dim3(p.block), 0, s, c->arena,
+                                   c->xy, k.ids, k.first_slot, k.payload, k.off, k.len, k.n, c->capacity, c->err,
+                                   c->sink, aux_args<IO>(k), cl);
+                hit = true;
+            }
+        },
+        ModeOf{p.mode}, BoolOf{p.frame}, IoOf{p.io});
+    return hit ? launched() : ZRC4_ERR_INTERNAL;
+}
+
+int launch_whole(zrc4_ctx *c, const CryptCall &k, const zrc4::CryptPlan &p, const zrc4::Claim &cl, hipStream_t s)
+{
+    bool hit = false;
+    with_constants(
+        [&](auto M, auto F, auto IO) {
+            if constexpr (zrc4::whole_form_exists(M, F, IO)) {
+                hipLaunchKernelGGL((zrc4::crypt_kernel<M, F, IO>), dim3(p.grid), dim3(p.block), 0, s, c->arena, c->xy,
+                                   k.ids, k.first_slot, k.payload, k.off, k.len, k.n, c->capacity, c->err, c->sink,
+                                   aux_args<IO>(k), cl);
+                hit = true;
+            }
+        },
+        ModeOf{p.mode}, BoolOf{p.frame}, IoOf{p.io});
+    return hit ? launched() : ZRC4_ERR_INTERNAL;
+}
+
+int launch_stream(zrc4_ctx *c, const CryptCall &k, const zrc4::CryptPlan &p, const zrc4::Claim &cl, hipStream_t s)
+{
+    bool hit = false;
+    with_constants(
+        [&](auto PF, auto GR, auto F) {
+            if constexpr (zrc4::stream_form_exists(PF, GR, F)) {
+                hipLaunchKernelGGL((zrc4::crypt_stream_kernel<PF, GR, F>), dim3(p.grid), dim3(p.block), 0, s,
+                                   c->arena, c->xy, k.ids, k.first_slot, k.payload, k.off, k.len, k.n, c->capacity,
+                                   c->err, c->sink, cl, aux_args<zrc4::kIoInPlace>(k));
+                hit = true;
+            }
+        },
+        BoolOf{p.pf}, BoolOf{p.gr}, BoolOf{p.frame});
+    return hit ? launched() : ZRC4_ERR_INTERNAL;
+}
+
+// A fresh claim tag per grouped launch; on the 32-bit wrap the words are
+// zeroed first (stream-ordered before this launch).
+int next_claim(zrc4_ctx *c, hipStream_t s, zrc4::Claim &cl)
+{
+    const size_t words = (size_t)(c->capacity / zrc4::kGroup) * zrc4::kClaimParts;
+    if (++c->epoch == 0u) {
+        ZRC4_TRY(hipMemsetAsync(c->claim, 0, words * 8u, s));
+        c->epoch = 1u;
+    }
+    cl = zrc4::Claim{c->claim, c->epoch, reinterpret_cast<const uint32_t *>(c->claim + words)};
+    return ZRC4_OK;
+}
+
+// Check the declared groups before the crypt launch (stream-ordered): a
+// disagreeing bucket's groups are claimed under this launch's epoch.  The
+// groups go through the context's ring of pinned buffers (zrc4_ctx::h_decl).
+int check_declared(zrc4_ctx *c, const CryptCall &k, uint32_t buckets, const zrc4::Claim &cl, hipStream_t s)
+{
+    const int r = (int)(c->decl_next++ % (uint32_t)zrc4_ctx::kDeclRing);
+    if (c->decl_ev_live[r]) ZRC4_TRY(hipEventSynchronize(c->decl_ev[r]));    // its last reader has run
+    if (!c->decl_ev[r] && hipEventCreateWithFlags(&c->decl_ev[r], hipEventDisableTiming) != hipSuccess)
+        return ZRC4_ERR_HIP;
+    if (buckets > c->h_decl_cap[r]) {
+        if (c->h_decl[r]) (void)hipHostFree(c->h_decl[r]);
+        c->h_decl[r] = nullptr;
+        c->h_decl_cap[r] = 0;
+        uint32_t want = 1024u;
+        while (want < buckets) want <<= 1;
+        void *p = nullptr;
+        if (hipHostMalloc(&p, (size_t)want * 4u, hipHostMallocCoherent) != hipSuccess) return ZRC4_ERR_OUT_OF_MEMORY;
+        c->h_decl[r] = static_cast<uint32_t *>(p);
+        c->h_decl_cap[r] = want;
+    }
+    memcpy(c->h_decl[r], k.decl, (size_t)buckets * 4u);
+    hipLaunchKernelGGL(zrc4::decl_check_kernel, dim3(buckets), dim3(zrc4::kGroup), 0, s, k.ids, k.len, k.n,
+                       c->h_decl[r], c->capacity, cl, c->err);
+    if (int rc = launched()) return rc;
+    ZRC4_TRY(hipEventRecord(c->decl_ev[r], s));
+    c->decl_ev_live[r] = true;
+    return ZRC4_OK;
+}
+
+// One planned launch: the claim epoch (grouped), the up-front check and the
+// pre-kernel the plan asks for, then the kernel.
+int issue_crypt(zrc4_ctx *c, const CryptCall &k, const zrc4::CryptPlan &p, hipStream_t s)
+{
+    int rc = ZRC4_OK;
+    zrc4::Claim cl{nullptr, 0u, nullptr};
+    if (k.mode == zrc4::kGrouped && (rc = next_claim(c, s, cl))) return rc;
+    if (p.check && (rc = check_declared(c, k, p.groups, cl, s))) return rc;
+    const uint32_t *span_ids = k.mode == zrc4::kGrouped ? k.ids : nullptr;
+    if (p.pre == zrc4::kPreFill)
+        hipLaunchKernelGGL(zrc4::span_fill_kernel, dim3(p.pre_grid), dim3(zrc4::kGroup), 0, s, span_ids, k.payload,
+                           k.off, k.len, k.n, c->capacity);
+    if (p.pre == zrc4::kPreCopy)
+        hipLaunchKernelGGL(zrc4::span_copy_kernel, dim3(p.pre_grid), dim3(zrc4::kGroup), 0, s, span_ids, k.src,
+                           k.src_off, k.payload, k.off, k.len, k.n, c->capacity);
+    if (p.pre != zrc4::kPreNone && (rc = launched())) return rc;
+    switch (p.family) {
+    case zrc4::kFamWin: return launch_win(c, k, p, cl, s);
+    case zrc4::kFamDecl: return launch_decl(c, k, p, cl, s);
+    case zrc4::kFamHalf: return launch_half(c, k, p, cl, s);
+    case zrc4::kFamWhole: return launch_whole(c, k, p, cl, s);
+    case zrc4::kFamStream: return launch_stream(c, k, p, cl, s);
+    }
+    return ZRC4_ERR_INTERNAL;
+}
+
+// Every crypt, keystream and out-of-place call: validate, plan (plan_crypt,
+// zrc4_plan.hpp: the rules and their measured reasons), then the plan's side
+// effects and its kernel (issue_crypt) -- once, or once per round where the
+// plan splits a rounds call into kIoTo calls on the stream.
+int launch_crypt(zrc4_ctx *c, const CryptCall &k, hipStream_t s)
+{
+    if (k.n == 0) return ZRC4_OK;
+    const bool out_of_place = k.io == zrc4::kIoTo || k.io == zrc4::kIoToRounds;
+    if (out_of_place && (!k.src || !k.src_off)) return ZRC4_ERR_INVALID_ARG;
+    zrc4::CryptShape sh{};
+    sh.mode = k.mode;
+    sh.first_aligned = (k.first_slot & 255u) == 0u;
+    sh.n = k.n;
+    sh.rounds = k.rounds;
+    sh.cus = (uint32_t)c->num_cus;
+    sh.frame = k.frame != nullptr;
+    sh.declared = k.decl != nullptr;
+    sh.trusted = k.trusted;
+    sh.io = k.io;
+    const zrc4::CryptPlan p = zrc4::plan_crypt(sh);
+    if (p.err != zrc4::kPlanOk) return ZRC4_ERR_INVALID_ARG;
+    if (k.mode == zrc4::kRange && (uint64_t)k.first_slot + k.n > c->capacity) return ZRC4_ERR_SLOT_RANGE;
+    if (!p.split) return issue_crypt(c, k, p, s);
+    CryptCall one = k;
+    one.io = zrc4::kIoTo;
+    one.rounds = 1;
+    for (uint32_t r = 0; r < k.rounds; ++r) {
+        const size_t at = (size_t)r * k.n;
+        one.off = k.off + at;
+        one.len = k.len + at;
+        one.src_off = k.src_off + at;
+        if (int rc = issue_crypt(c, one, p, s)) return rc;
+    }
+    return ZRC4_OK;
 }
 
 int launch_ksa(zrc4_ctx *c, const uint32_t *ids, uint32_t first_slot, const uint8_t *keys,
@@ -424,7 +374,7 @@ int launch_ksa(zrc4_ctx *c, const uint32_t *ids, uint32_t first_slot, const uint
     const uint32_t grid = (n + zrc4::kGroup - 1) / zrc4::kGroup;
     hipLaunchKernelGGL(zrc4::ksa_kernel, dim3(grid), dim3(zrc4::kGroup), 0, s, c->arena, c->xy,
                        ids, first_slot, keys, key_off, key_len, n, c->capacity, c->err);
-    return hipGetLastError() == hipSuccess ? ZRC4_OK : ZRC4_ERR_LAUNCH;
+    return launched();
 }
 
 // Record export / import (zrc4_export_states and friends; kernels and paths:
@@ -455,7 +405,7 @@ int launch_export(zrc4_ctx *c, const uint32_t *ids, uint32_t first_slot, uint32_
         hipLaunchKernelGGL(zrc4::states_export_kernel<false>, dim3(buckets), dim3(zrc4::kGroup), 0, s, c->arena,
                            c->xy, ids, 0u, n, c->capacity, sbox, xy, c->err);
     }
-    return hipGetLastError() == hipSuccess ? ZRC4_OK : ZRC4_ERR_LAUNCH;
+    return launched();
 }
 
 int launch_import(zrc4_ctx *c, const uint32_t *ids, uint32_t first_slot, uint32_t n, const uint8_t *sbox,
@@ -472,7 +422,7 @@ int launch_import(zrc4_ctx *c, const uint32_t *ids, uint32_t first_slot, uint32_
         hipLaunchKernelGGL(zrc4::states_scatter_kernel, dim3(grid), dim3(256), 0, s, c->arena, c->xy, ids, n,
                            c->capacity, sbox, xy, gate, gate_cap, c->err);
     }
-    return hipGetLastError() == hipSuccess ? ZRC4_OK : ZRC4_ERR_LAUNCH;
+    return launched();
 }
 
 // The per-iteration completion point of the session engine's hooks: ONE
@@ -586,7 +536,8 @@ int zrc4_crypt(zrc4_ctx *c, const uint32_t *ids, uint8_t *payload, const uint64_
     if (n && (!payload || !off || !len)) return ZRC4_ERR_INVALID_ARG;
     int rc = set_device(c);
     if (rc) return rc;
-    return launch_crypt(c, ids ? zrc4::kIds : zrc4::kRange, ids, 0, payload, off, len, n, (hipStream_t)stream);
+    return launch_crypt(c, crypt_call(ids ? zrc4::kIds : zrc4::kRange, ids, 0, payload, off, len, n),
+                        (hipStream_t)stream);
 }
 
 int zrc4_ksa_range(zrc4_ctx *c, uint32_t first_slot, const uint8_t *keys,
@@ -606,7 +557,7 @@ int zrc4_crypt_range(zrc4_ctx *c, uint32_t first_slot, uint8_t *payload, const u
     if (n && (!payload || !off || !len)) return ZRC4_ERR_INVALID_ARG;
     int rc = set_device(c);
     if (rc) return rc;
-    return launch_crypt(c, zrc4::kRange, nullptr, first_slot, payload, off, len, n, (hipStream_t)stream);
+    return launch_crypt(c, crypt_call(zrc4::kRange, nullptr, first_slot, payload, off, len, n), (hipStream_t)stream);
 }
 
 int zrc4_crypt_grouped(zrc4_ctx *c, const uint32_t *ids, uint8_t *payload, const uint64_t *off,
@@ -616,10 +567,22 @@ int zrc4_crypt_grouped(zrc4_ctx *c, const uint32_t *ids, uint8_t *payload, const
     if (n && (!ids || !payload || !off || !len)) return ZRC4_ERR_INVALID_ARG;
     int rc = set_device(c);
     if (rc) return rc;
-    return launch_crypt(c, zrc4::kGrouped, ids, 0, payload, off, len, n, (hipStream_t)stream);
+    return launch_crypt(c, crypt_call(zrc4::kGrouped, ids, 0, payload, off, len, n), (hipStream_t)stream);
 }
 
 namespace {
+// A call's declared bucket groups (none declared: fine): each names a group of
+// the arena, or ZRC4_IDLE_SLOT for a bucket with no busy entry.
+bool bucket_groups_ok(const zrc4_ctx *c, const uint32_t *bucket_group, uint32_t n)
+{
+    if (!bucket_group) return true;
+    const uint32_t nb = (uint32_t)(((uint64_t)n + zrc4::kGroup - 1) / zrc4::kGroup);
+    const uint32_t groups = c->capacity / zrc4::kGroup;
+    for (uint32_t b = 0; b < nb; ++b)
+        if (bucket_group[b] >= groups && bucket_group[b] != ZRC4_IDLE_SLOT) return false;
+    return true;
+}
+
 int frame_args(const zrc4_frame_args *f, uint32_t n, zrc4::FrameArgs &out)
 {
     if (!f) return ZRC4_ERR_INVALID_ARG;
@@ -646,7 +609,9 @@ int zrc4_crypt_range_frame(zrc4_ctx *c, uint32_t first_slot, uint8_t *payload, c
     int rc = frame_args(frame, n, fr);
     if (rc) return rc;
     if ((rc = set_device(c))) return rc;
-    return launch_crypt(c, zrc4::kRange, nullptr, first_slot, payload, off, len, n, (hipStream_t)stream, &fr);
+    CryptCall k = crypt_call(zrc4::kRange, nullptr, first_slot, payload, off, len, n);
+    k.frame = &fr;
+    return launch_crypt(c, k, (hipStream_t)stream);
 }
 
 int zrc4_crypt_grouped_frame(zrc4_ctx *c, const uint32_t *ids, uint8_t *payload, const uint64_t *off,
@@ -658,7 +623,9 @@ int zrc4_crypt_grouped_frame(zrc4_ctx *c, const uint32_t *ids, uint8_t *payload,
     int rc = frame_args(frame, n, fr);
     if (rc) return rc;
     if ((rc = set_device(c))) return rc;
-    return launch_crypt(c, zrc4::kGrouped, ids, 0, payload, off, len, n, (hipStream_t)stream, &fr);
+    CryptCall k = crypt_call(zrc4::kGrouped, ids, 0, payload, off, len, n);
+    k.frame = &fr;
+    return launch_crypt(c, k, (hipStream_t)stream);
 }
 
 int zrc4_crypt_grouped_declared(zrc4_ctx *c, const uint32_t *ids, const uint32_t *bucket_group, uint8_t *payload,
@@ -667,16 +634,15 @@ int zrc4_crypt_grouped_declared(zrc4_ctx *c, const uint32_t *ids, const uint32_t
 {
     if (!c) return ZRC4_ERR_INVALID_ARG;
     if (n && (!ids || !bucket_group || !payload || !off || !len)) return ZRC4_ERR_INVALID_ARG;
-    const uint32_t nb = (uint32_t)(((uint64_t)n + zrc4::kGroup - 1) / zrc4::kGroup);
-    const uint32_t groups = c->capacity / zrc4::kGroup;
-    for (uint32_t b = 0; b < nb; ++b)
-        if (bucket_group[b] >= groups && bucket_group[b] != ZRC4_IDLE_SLOT) return ZRC4_ERR_INVALID_ARG;
+    if (!bucket_groups_ok(c, bucket_group, n)) return ZRC4_ERR_INVALID_ARG;
     zrc4::FrameArgs fr;
     int rc = frame ? frame_args(frame, n, fr) : ZRC4_OK;
     if (rc) return rc;
     if ((rc = set_device(c))) return rc;
-    return launch_crypt(c, zrc4::kGrouped, ids, 0, payload, off, len, n, (hipStream_t)stream, frame ? &fr : nullptr,
-                        bucket_group);
+    CryptCall k = crypt_call(zrc4::kGrouped, ids, 0, payload, off, len, n);
+    k.frame = frame ? &fr : nullptr;
+    k.decl = bucket_group;
+    return launch_crypt(c, k, (hipStream_t)stream);
 }
 
 int zrc4_keystream_range(zrc4_ctx *c, uint32_t first_slot, uint8_t *out, const uint64_t *off, const uint32_t *len,
@@ -686,8 +652,9 @@ int zrc4_keystream_range(zrc4_ctx *c, uint32_t first_slot, uint8_t *out, const u
     if (n && (!out || !off || !len)) return ZRC4_ERR_INVALID_ARG;
     int rc = set_device(c);
     if (rc) return rc;
-    return launch_crypt(c, zrc4::kRange, nullptr, first_slot, out, off, len, n, (hipStream_t)stream, nullptr, nullptr,
-                        false, zrc4::kIoKs);
+    CryptCall k = crypt_call(zrc4::kRange, nullptr, first_slot, out, off, len, n);
+    k.io = zrc4::kIoKs;
+    return launch_crypt(c, k, (hipStream_t)stream);
 }
 
 int zrc4_keystream_grouped(zrc4_ctx *c, const uint32_t *ids, const uint32_t *bucket_group, uint8_t *out,
@@ -695,16 +662,13 @@ int zrc4_keystream_grouped(zrc4_ctx *c, const uint32_t *ids, const uint32_t *buc
 {
     if (!c) return ZRC4_ERR_INVALID_ARG;
     if (n && (!ids || !out || !off || !len)) return ZRC4_ERR_INVALID_ARG;
-    if (bucket_group) {
-        const uint32_t nb = (uint32_t)(((uint64_t)n + zrc4::kGroup - 1) / zrc4::kGroup);
-        const uint32_t groups = c->capacity / zrc4::kGroup;
-        for (uint32_t b = 0; b < nb; ++b)
-            if (bucket_group[b] >= groups && bucket_group[b] != ZRC4_IDLE_SLOT) return ZRC4_ERR_INVALID_ARG;
-    }
+    if (!bucket_groups_ok(c, bucket_group, n)) return ZRC4_ERR_INVALID_ARG;
     int rc = set_device(c);
     if (rc) return rc;
-    return launch_crypt(c, zrc4::kGrouped, ids, 0, out, off, len, n, (hipStream_t)stream, nullptr, bucket_group, false,
-                        zrc4::kIoKs);
+    CryptCall k = crypt_call(zrc4::kGrouped, ids, 0, out, off, len, n);
+    k.decl = bucket_group;
+    k.io = zrc4::kIoKs;
+    return launch_crypt(c, k, (hipStream_t)stream);
 }
 
 int zrc4_crypt_to_range(zrc4_ctx *c, uint32_t first_slot, const uint8_t *src, const uint64_t *src_off, uint8_t *dst,
@@ -714,8 +678,11 @@ int zrc4_crypt_to_range(zrc4_ctx *c, uint32_t first_slot, const uint8_t *src, co
     if (n && (!src || !src_off || !dst || !dst_off || !len)) return ZRC4_ERR_INVALID_ARG;
     int rc = set_device(c);
     if (rc) return rc;
-    return launch_crypt(c, zrc4::kRange, nullptr, first_slot, dst, dst_off, len, n, (hipStream_t)stream, nullptr,
-                        nullptr, false, zrc4::kIoTo, src, src_off);
+    CryptCall k = crypt_call(zrc4::kRange, nullptr, first_slot, dst, dst_off, len, n);
+    k.io = zrc4::kIoTo;
+    k.src = src;
+    k.src_off = src_off;
+    return launch_crypt(c, k, (hipStream_t)stream);
 }
 
 int zrc4_crypt_to_grouped(zrc4_ctx *c, const uint32_t *ids, const uint32_t *bucket_group, const uint8_t *src,
@@ -724,16 +691,15 @@ int zrc4_crypt_to_grouped(zrc4_ctx *c, const uint32_t *ids, const uint32_t *buck
 {
     if (!c) return ZRC4_ERR_INVALID_ARG;
     if (n && (!ids || !src || !src_off || !dst || !dst_off || !len)) return ZRC4_ERR_INVALID_ARG;
-    if (bucket_group) {
-        const uint32_t nb = (uint32_t)(((uint64_t)n + zrc4::kGroup - 1) / zrc4::kGroup);
-        const uint32_t groups = c->capacity / zrc4::kGroup;
-        for (uint32_t b = 0; b < nb; ++b)
-            if (bucket_group[b] >= groups && bucket_group[b] != ZRC4_IDLE_SLOT) return ZRC4_ERR_INVALID_ARG;
-    }
+    if (!bucket_groups_ok(c, bucket_group, n)) return ZRC4_ERR_INVALID_ARG;
     int rc = set_device(c);
     if (rc) return rc;
-    return launch_crypt(c, zrc4::kGrouped, ids, 0, dst, dst_off, len, n, (hipStream_t)stream, nullptr, bucket_group,
-                        false, zrc4::kIoTo, src, src_off);
+    CryptCall k = crypt_call(zrc4::kGrouped, ids, 0, dst, dst_off, len, n);
+    k.decl = bucket_group;
+    k.io = zrc4::kIoTo;
+    k.src = src;
+    k.src_off = src_off;
+    return launch_crypt(c, k, (hipStream_t)stream);
 }
 
 int zrc4_crypt_to_range_rounds(zrc4_ctx *c, uint32_t first_slot, const uint8_t *src, const uint64_t *src_off,
@@ -746,8 +712,12 @@ int zrc4_crypt_to_range_rounds(zrc4_ctx *c, uint32_t first_slot, const uint8_t *
     if (n && (!src || !src_off || !dst || !dst_off || !len)) return ZRC4_ERR_INVALID_ARG;
     int rc = set_device(c);
     if (rc) return rc;
-    return launch_crypt(c, zrc4::kRange, nullptr, first_slot, dst, dst_off, len, n, (hipStream_t)stream, nullptr,
-                        nullptr, false, zrc4::kIoToRounds, src, src_off, rounds);
+    CryptCall k = crypt_call(zrc4::kRange, nullptr, first_slot, dst, dst_off, len, n);
+    k.io = zrc4::kIoToRounds;
+    k.src = src;
+    k.src_off = src_off;
+    k.rounds = rounds;
+    return launch_crypt(c, k, (hipStream_t)stream);
 }
 
 int zrc4_crypt_to_grouped_rounds(zrc4_ctx *c, const uint32_t *ids, const uint32_t *bucket_group, const uint8_t *src,
@@ -758,16 +728,16 @@ int zrc4_crypt_to_grouped_rounds(zrc4_ctx *c, const uint32_t *ids, const uint32_
     if (rounds == 0u || rounds > ZRC4_MAX_ROUNDS || (uint64_t)n * rounds > 0xFFF00000u) return ZRC4_ERR_INVALID_ARG;
     if (rounds == 1u) return zrc4_crypt_to_grouped(c, ids, bucket_group, src, src_off, dst, dst_off, len, n, stream);
     if (n && (!ids || !src || !src_off || !dst || !dst_off || !len)) return ZRC4_ERR_INVALID_ARG;
-    if (bucket_group) {
-        const uint32_t nb = (uint32_t)(((uint64_t)n + zrc4::kGroup - 1) / zrc4::kGroup);
-        const uint32_t groups = c->capacity / zrc4::kGroup;
-        for (uint32_t b = 0; b < nb; ++b)
-            if (bucket_group[b] >= groups && bucket_group[b] != ZRC4_IDLE_SLOT) return ZRC4_ERR_INVALID_ARG;
-    }
+    if (!bucket_groups_ok(c, bucket_group, n)) return ZRC4_ERR_INVALID_ARG;
     int rc = set_device(c);
     if (rc) return rc;
-    return launch_crypt(c, zrc4::kGrouped, ids, 0, dst, dst_off, len, n, (hipStream_t)stream, nullptr, bucket_group,
-                        false, zrc4::kIoToRounds, src, src_off, rounds);
+    CryptCall k = crypt_call(zrc4::kGrouped, ids, 0, dst, dst_off, len, n);
+    k.decl = bucket_group;
+    k.io = zrc4::kIoToRounds;
+    k.src = src;
+    k.src_off = src_off;
+    k.rounds = rounds;
+    return launch_crypt(c, k, (hipStream_t)stream);
 }
 
 int zrc4_xor_ring(zrc4_ctx *c, uint8_t *ring, uint32_t ring_cap, const uint32_t *rid,
@@ -781,7 +751,7 @@ int zrc4_xor_ring(zrc4_ctx *c, uint8_t *ring, uint32_t ring_cap, const uint32_t 
     if (rc) return rc;
     hipLaunchKernelGGL(zrc4::xor_ring_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, ring, ring_cap,
                        rid, pos, payload, off, len, n);
-    return hipGetLastError() == hipSuccess ? ZRC4_OK : ZRC4_ERR_LAUNCH;
+    return launched();
 }
 
 int zrc4_frame_scan(zrc4_ctx *c, const uint8_t *buf, const uint64_t *off, const uint32_t *len,
@@ -796,7 +766,7 @@ int zrc4_frame_scan(zrc4_ctx *c, const uint8_t *buf, const uint64_t *off, const 
     if (rc) return rc;
     hipLaunchKernelGGL(zrc4::frame_scan_kernel, dim3((n + 255u) / 256u), dim3(256), 0, (hipStream_t)stream,
                        buf, off, len, bound, n, max_packets, npk, used, status, max_packets ? pkt_len : nullptr);
-    return hipGetLastError() == hipSuccess ? ZRC4_OK : ZRC4_ERR_LAUNCH;
+    return launched();
 }
 
 int zrc4_poll_faults(zrc4_ctx *c)
@@ -1028,10 +998,12 @@ int zrc4_crypt_host(zrc4_ctx *c, const uint32_t *ids, uint8_t *payload, size_t p
             st = c->d_stage;
         }
     }
-    rc = launch_crypt(c, grouped ? zrc4::kGrouped : ids ? zrc4::kIds : zrc4::kRange,
-                      ids ? (const uint32_t *)(st + o_ids) : nullptr, 0, st + o_pay, (const uint64_t *)(st + o_off),
-                      (const uint32_t *)(st + o_len), m, c->stream, nullptr, grouped ? bgroup.data() : nullptr,
-                      true);
+    CryptCall k = crypt_call(grouped ? zrc4::kGrouped : ids ? zrc4::kIds : zrc4::kRange,
+                             ids ? (const uint32_t *)(st + o_ids) : nullptr, 0, st + o_pay,
+                             (const uint64_t *)(st + o_off), (const uint32_t *)(st + o_len), m);
+    k.decl = grouped ? bgroup.data() : nullptr;
+    k.trusted = true;
+    rc = launch_crypt(c, k, c->stream);
     if (rc) {
         // whatever was queued before the failure (the H2D copies, a check
         // kernel reading the zero-copy tables) still reads the staging

@@ -30,10 +30,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "zrc4_plan.hpp"   // kGroup, CryptMode, CryptIo, kBodyMaxBuckets, kHalfBlock
 
 namespace zrc4 {
 
-constexpr int kGroup = 256;            // slots per workgroup / arena group
 constexpr int kGroupBytes = 256 * 256; // 64 KiB S-box image per group
 
 // Fault latch: words in pinned host memory, one per fault kind; every
@@ -679,20 +679,6 @@ __device__ __forceinline__ void round_wait_asm(uint32_t &nl, uint64_t &no, uint6
     asm volatile("s_waitcnt vmcnt(0)" : "+v"(nl), "+v"(no), "+v"(ns) :: "memory");
 }
 
-// The I/O form of a crypt kernel (last template parameter of the window, half-
-// group, whole-group and declared kernels):
-//   kIoInPlace  the span is read, XORed and written back (zrc4_crypt_*);
-//   kIoKs       write-only keystream (zrc4_keystream_*): the span is stored
-//               and never read;
-//   kIoTo       out of place (zrc4_crypt_to_*): entry i reads its SOURCE span
-//               and stores the XOR to its destination span; the destination
-//               is never read and the source never written;
-//   kIoToRounds kIoTo, `rounds` times in one launch (zrc4_crypt_to_*_rounds;
-//               the lane-per-stream kernels only): the group image is loaded
-//               and stored once, and each lane walks its slot's `rounds`
-//               entries in order (crypt_body).
-enum CryptIo : int { kIoInPlace = 0, kIoKs = 1, kIoTo = 2, kIoToRounds = 3 };
-
 // Crypt one lane's message in place: unaligned head bytes, 64-byte blocks
 // (crypt_blocks_asm), 16-byte chunks, tail bytes.  If `pre` is set, A already
 // holds the first 64-byte block (issued by the caller ahead of the LDS fill).
@@ -1256,8 +1242,8 @@ __device__ __forceinline__ void issue_image_asm(u32x32 &ilo, u32x32 &ihi, const 
 // each moves a 32 KiB half image.  The workgroup reserves more LDS than it
 // uses so that no two share a CU: at 2 waves per CU a chain step takes
 // 41.2 us per KiB against 43.1 at 4 (profiles/r02/tl_waves.log).
+// (enum CryptMode: zrc4_plan.hpp)
 // ---------------------------------------------------------------------------
-enum CryptMode : int { kIds = 0, kRange = 1, kGrouped = 2 };
 
 // ---------------------------------------------------------------------------
 // proto4z framing of decrypted session buffers:
@@ -1427,8 +1413,7 @@ __device__ __forceinline__ uint32_t xcd_run_map(uint32_t k, uint32_t grid)
 // Declared bucket groups of a grouped launch of at most 256 buckets on the
 // half-group and whole-group kernels (zrc4_crypt_grouped_declared): bucket
 // b's group, ZRC4_INVALID for a bucket with no busy entry.  By value, so it
-// sits in the kernel-argument segment (1 KiB).
-constexpr uint32_t kBodyMaxBuckets = 256;
+// sits in the kernel-argument segment (1 KiB; kBodyMaxBuckets: zrc4_plan.hpp).
 struct BucketGroups {
     uint32_t g[kBodyMaxBuckets];
 };
@@ -1856,11 +1841,7 @@ crypt_decl_kernel(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy,
                                                 &dg);
 }
 
-// Half-group workgroups (kRange / kGrouped, few groups): one per CU;
-// workgroup 2w + h runs half h of bucket w.  Launched with 256 threads, of
-// which the two waves that work are picked by SIMD (crypt_body).
-constexpr uint32_t kHalfBlock = 256u;
-
+// Half-group workgroups (kHalfBlock threads: zrc4_plan.hpp).
 template <int MODE, bool FRAME = false, int IO = kIoInPlace>
 __global__ void __launch_bounds__(kHalfBlock, 1)
 crypt_half_kernel(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy,

@@ -9,7 +9,7 @@
 // committed ring bytes on the host and goes to the device only for what the
 // ring does not cover (a "tail", e.g. a slot's first call after makeSBox).
 // Refills run in the background on their own stream: one write-only grouped
-// launch (launch_crypt's ks mode, the path of zrc4_keystream_grouped) that
+// launch (launch_crypt with io = kIoKs, the path of zrc4_keystream_grouped) that
 // STORES the next keystream bytes of every slot used since the last refill
 // into its ring, whatever the ring held -- it is never read by the device and
 // never zeroed by the host -- at most kDepth queued, committed when their
@@ -227,11 +227,14 @@ struct zrc4_ks {
         if (es.empty()) return ZRC4_OK;
         // (the groups built here are declared to the launch; trusted: no
         // up-front check above 256 buckets, where they are not used)
-        int rc = R.t.build(es) ? (set_device(c) ? ZRC4_ERR_HIP
-                                                : launch_crypt(c, zrc4::kGrouped, R.t.ids.p, 0, base, R.t.off.p,
-                                                               R.t.len.p, R.t.n, sB, nullptr, R.t.groups.data(), true,
-                                                               zrc4::kIoKs))
-                               : ZRC4_ERR_OUT_OF_MEMORY;
+        int rc = R.t.build(es) ? (set_device(c) ? ZRC4_ERR_HIP : ZRC4_OK) : ZRC4_ERR_OUT_OF_MEMORY;
+        if (rc == ZRC4_OK) {
+            CryptCall k = crypt_call(zrc4::kGrouped, R.t.ids.p, 0, base, R.t.off.p, R.t.len.p, R.t.n);
+            k.decl = R.t.groups.data();
+            k.trusted = true;
+            k.io = zrc4::kIoKs;
+            rc = launch_crypt(c, k, sB);
+        }
         if (rc != ZRC4_OK) {                      // nothing queued: the levels go back
             for (const KsEntry &e : es) lv[e.slot].pend -= e.len;
             return rc;

@@ -37,6 +37,7 @@
 // column q = 32h + L.
 #pragma once
 #include "zrc4_kernels.hpp"
+#include "zrc4_plan.hpp"
 
 namespace zrc4 {
 
@@ -204,8 +205,8 @@ __device__ __forceinline__ void win_windows(WinLane &w, uint32_t rem, uint32_t l
 // Declared bucket groups of a grouped window launch (zrc4_crypt_grouped_declared):
 // bucket b's group, or ZRC4_INVALID for a bucket with no busy entry.  Passed
 // by value, so it sits in the kernel-argument segment and is read with the
-// launch's other arguments: no dependent memory round trip before the image.
-constexpr uint32_t kWinMaxBuckets = 32;      // bench.py's WIN_MAX_GROUPS mirrors this constant
+// launch's other arguments: no dependent memory round trip before the image
+// (kWinMaxBuckets: zrc4_plan.hpp).
 struct WinGroups {
     uint32_t g[kWinMaxBuckets];
 };
