@@ -28,6 +28,11 @@
  *   - ids == NULL means the identity map (batch entry i -> slot i).
  *   - a slot may appear at most once per call; len == 0 is a no-op for that
  *     slot (reference: `length <= 0` never enters the loop, :81).
+ *   - every `base + off` (payload + off[i], keys + key_off[i], src + src_off[i],
+ *     dst + dst_off[i], frame->off[i], ring + rid * ring_cap) is computed
+ *     modulo 2^64, so an offset may be the two's-complement difference of an
+ *     address BELOW the base: one base pointer serves spans anywhere in the
+ *     address space, on either side of it and of any multiple of 2^32.
  *   - calls on one context are serialised by the caller (one event-loop
  *     thread, as the reference: include/zsummerX/frame/manager.h:98-110);
  *     concurrent calls on different streams must touch disjoint 256-slot

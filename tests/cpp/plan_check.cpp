@@ -8,12 +8,16 @@
 //   plan_check classes   the family of every in-place, undeclared range and
 //                        grouped shape of the sweep, one per line:
 //                        mode first_aligned G cus frame family
+//   plan_check plan ...  the plan of each shape given on the command line
+//                        (tests/test_gpu_addressing.py checks its own statement
+//                        of the family against it)
 //
 // The table's expectations are written out by hand from the rules the
 // dispatch had as one if-chain in zrc4.hip; none is computed by plan_crypt.
 #include "zrc4_plan.hpp"
 
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include <set>
@@ -265,6 +269,27 @@ int print_classes()
     return 0;
 }
 
+// plan_check plan <mode> <first_aligned> <n> <cus> <frame> <decl> <io> <rounds> ...
+// (any number of such groups of eight): one line per shape,
+//   family kernel-name pre split
+// or "error" where plan_crypt refuses the shape.
+int print_plans(int argc, char **argv)
+{
+    static const char *const kFam[] = {"win", "decl", "half", "whole", "stream"};
+    if (argc < 8 || argc % 8) return 2;
+    for (int a = 0; a < argc; a += 8) {
+        unsigned long v[8];
+        for (int i = 0; i < 8; ++i) v[i] = strtoul(argv[a + i], nullptr, 10);
+        const CryptPlan p = plan_crypt(shape((int)v[0], v[1] != 0, (uint32_t)v[2], (uint32_t)v[3], v[4] != 0,
+                                             (int)v[5], (int)v[6], (uint32_t)v[7]));
+        if (p.err != kPlanOk)
+            printf("error\n");
+        else
+            printf("%s %s %d %d\n", kFam[p.family], p.name().s, p.pre, (int)p.split);
+    }
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char **argv)
@@ -272,6 +297,7 @@ int main(int argc, char **argv)
     if (argc < 2) return check_table();
     if (!strcmp(argv[1], "sweep")) return check_sweep();
     if (!strcmp(argv[1], "classes")) return print_classes();
-    fprintf(stderr, "usage: plan_check [sweep | classes]\n");
+    if (!strcmp(argv[1], "plan")) return print_plans(argc - 2, argv + 2);
+    fprintf(stderr, "usage: plan_check [sweep | classes | plan <8 numbers per shape>]\n");
     return 2;
 }
