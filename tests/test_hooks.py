@@ -101,6 +101,18 @@ def test_adaptive_mode_off_emulated(tools):
     assert out["hooks"]["direct_calls"] == 0 and out["hooks"]["direct_bytes"] == 0, out["hooks"]
 
 
+@pytest.mark.parametrize("seed", [1, 2, 3, 4, 5])
+def test_reservoir_core_alone(tools, seed):
+    """The reservoir core both owners share (csrc/zrc4_reservoir.hpp) over HIP
+    runtime stubs that can fail (tests/cpp/reservoir_check.cpp): level
+    invariants after every operation, every byte handed out against the oracle
+    keystream, and each failure path (pinned memory exhausted, launch refused,
+    event not recordable, query / wait errors) leaving the levels as the
+    header promises -- paths no GPU test may provoke."""
+    out = run(tools / "reservoir_check_emu", seed)
+    assert out["ring_bytes"] > 0 and out["tail_bytes"] > 0 and out["refill_launches"] > 0, out
+
+
 def test_direct_host_logic_emulated(tools):
     run(tools / "hooks_check_emu", "direct", 16, 40, 9)
 

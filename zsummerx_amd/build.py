@@ -29,12 +29,14 @@ STRESS = PKG / "bin" / "frame_stress"
 ENGINE = PKG / "engine"
 FRAME_SOURCES = [ENGINE / "frame.cpp", ENGINE / "rc4_hooks_device.cpp"]
 FRAME_DEPS = FRAME_SOURCES + [ROOT / "include" / "zsummerx_amd" / "frame.h",
-                              ROOT / "include" / "zsummerx_amd" / "rc4_hooks.h", ROOT / "include" / "zrc4.h"]
+                              ROOT / "include" / "zsummerx_amd" / "rc4_hooks.h", ROOT / "include" / "zrc4.h",
+                              CSRC / "zrc4_reservoir.hpp"]
 ROCM = Path(os.environ.get("ROCM_PATH", "/opt/rocm"))
 
 # Everything under csrc/ that libzrc4.so is compiled from: the translation unit
 # first, then what it includes.
-HIP_CSRC = ("zrc4.hip", "zrc4_plan.hpp", "zrc4_kernels.hpp", "zrc4_win.hpp", "zrc4_line_loop.inc", "zrc4_ks.inc")
+HIP_CSRC = ("zrc4.hip", "zrc4_plan.hpp", "zrc4_kernels.hpp", "zrc4_win.hpp", "zrc4_line_loop.inc", "zrc4_ks.inc",
+            "zrc4_reservoir.hpp")
 HIP_SOURCES = [CSRC / HIP_CSRC[0]]
 HIP_DEPS = [CSRC / f for f in HIP_CSRC] + [ROOT / "include" / "zrc4.h"]
 
@@ -125,7 +127,7 @@ def build_frame(force: bool = False) -> Path:
     lib = build_lib(force)
     if force or _stale(FRAME, FRAME_DEPS + [lib]):
         cmd = ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra", "-Wno-unused-parameter",
-               "-D__HIP_PLATFORM_AMD__", f"-I{ROOT / 'include'}", f"-I{ROCM / 'include'}",
+               "-D__HIP_PLATFORM_AMD__", f"-I{ROOT / 'include'}", f"-I{CSRC}", f"-I{ROCM / 'include'}",
                "-o", str(FRAME), *map(str, FRAME_SOURCES),
                f"-L{PKG}", "-lzrc4", f"-L{ROCM / 'lib'}", "-lamdhip64",
                "-Wl,-rpath,$ORIGIN", f"-Wl,-rpath,{ROCM / 'lib'}"]
@@ -157,10 +159,13 @@ def build_test_tools(force: bool = False, sanitize: bool | str = False) -> Path:
       tools/bin/emu_keystream_check the emulated write-only keystream calls
                                  (tests/cpp/emu_zrc4_keystream.cpp) against
                                  the oracle and the header's rules
+      tools/bin/reservoir_check_emu csrc/zrc4_reservoir.hpp alone over its own HIP
+                                 runtime stubs with failure switches
+                                 (tests/cpp/reservoir_check.cpp)
       tools/bin/plan_check       csrc/zrc4_plan.hpp alone (g++, no HIP): the
                                  kernel choice against a hand-written table,
                                  and the plans of a shape sweep as text
-    sanitize=True builds only the two emulated binaries and plan_check, with
+    sanitize=True builds only the three *_emu binaries and plan_check, with
     ASan + UBSan, into tools/bin/san/ (scripts/sanitize.sh runs the CPU suites on them);
     sanitize="thread" the same with ThreadSanitizer into tools/bin/tsan/ (the
     reservoir's XOR worker threads)."""
@@ -175,8 +180,9 @@ def build_test_tools(force: bool = False, sanitize: bool | str = False) -> Path:
     ks_chk = ROOT / "tests" / "cpp" / "emu_keystream_check.cpp"
     dev = ENGINE / "rc4_hooks_device.cpp"
     plan_chk = ROOT / "tests" / "cpp" / "plan_check.cpp"
+    res_chk = ROOT / "tests" / "cpp" / "reservoir_check.cpp"
     common = ["-std=c++17", f"-I{ROOT / 'include'}", f"-I{ROOT / 'oracle'}"]
-    emu_flags = ["-D__HIP_PLATFORM_AMD__", f"-I{ROCM / 'include'}"]
+    emu_flags = ["-D__HIP_PLATFORM_AMD__", f"-I{CSRC}", f"-I{ROCM / 'include'}"]
     oracle_link = [f"-L{ROOT / 'oracle'}", "-loracle", "-Wl,-rpath,$ORIGIN/../../oracle"]
     jobs = [
         (out / "hooks_check", [chk, orc, frame] + FRAME_DEPS,
@@ -196,8 +202,13 @@ def build_test_tools(force: bool = False, sanitize: bool | str = False) -> Path:
          ["g++", "-O2", *common, *emu_flags, "-o", str(out / "frame_stress_emu"), str(ROOT / "tools" / "frame_stress.cpp"),
           *map(str, FRAME_SOURCES), str(emu), str(emu_ks), *oracle_link, "-ldl", "-lpthread"]),
     ]
-    # (an older tests/ tree run against this build has no plan_check.cpp and
-    # no test that asks for the binary: then there is nothing to build)
+    # (an older tests/ tree run against this build has no reservoir_check.cpp
+    # or plan_check.cpp and no test that asks for the binary: then there is
+    # nothing to build)
+    if res_chk.exists():
+        jobs.append((out / "reservoir_check_emu", [orc, res_chk, CSRC / "zrc4_reservoir.hpp", ROOT / "include" / "zrc4.h"],
+                     ["g++", "-O2", "-Wall", "-Wextra", *common, *emu_flags, "-o", str(out / "reservoir_check_emu"),
+                      str(res_chk), *oracle_link]))
     if plan_chk.exists():
         jobs.append((out / "plan_check", [plan_chk, CSRC / "zrc4_plan.hpp"],
                      ["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", f"-I{CSRC}", "-o", str(out / "plan_check"),

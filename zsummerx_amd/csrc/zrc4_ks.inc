@@ -3,143 +3,41 @@
 //
 // The per-call RC4Encryption::encryption (rc4_encryption.h:74-93) of the C++
 // mirror used to be one launch and one wait per call: ~15 us of round trip
-// plus the serial chain of the call's bytes.  RC4's keystream does not depend
-// on the data, so a reservoir keeps, per slot, keystream the device generated
-// AHEAD into a ring of pinned host memory; a call XORs the caller's bytes with
-// committed ring bytes on the host and goes to the device only for what the
-// ring does not cover (a "tail", e.g. a slot's first call after makeSBox).
-// Refills run in the background on their own stream: one write-only grouped
-// launch (launch_crypt with io = kIoKs, the path of zrc4_keystream_grouped) that
-// STORES the next keystream bytes of every slot used since the last refill
-// into its ring, whatever the ring held -- it is never read by the device and
-// never zeroed by the host -- at most kDepth queued, committed when their
-// event has completed.
-// The RC4 state never leaves the device and keystream bytes are consumed in
-// order, so every output byte is the reference's.
+// plus the serial chain of the call's bytes.  A reservoir keeps keystream the
+// device generated AHEAD in pinned host rings, so a call is a host XOR and goes
+// to the device only for what its ring does not cover (a "tail", e.g. a slot's
+// first call after makeSBox).  The RC4 state never leaves the device and
+// keystream bytes are consumed in order, so every output byte is the reference's.
 //
-// Invariants (per slot: gen = end of committed keystream, use = bytes
-// consumed, pend = end of queued refills; the device state sits at pend):
-//   * the host reads only ring bytes in [use, gen); refills write only
-//     [pend, pend + chunk), which the ring size keeps clear of [use, gen).
-//     The levels alone say which ring bytes hold keystream: consumed bytes
-//     (and a reseeded slot's dropped ones) stay in the ring, stale, until a
-//     later refill overwrites them;
-//   * a tail crypt, a reseed or a state copy first drains every queued refill
-//     (a grouped kernel stores whole 64 KiB group images), then gen = pend =
-//     use for the slots it touches;
+// The levels, rings, hungry list, refill queue and their ordering rules are the
+// reservoir core's (zrc4_reservoir.hpp: the design and its invariants are
+// stated there), shared with the session engine's hooks
+// (zsummerx_amd/engine/rc4_hooks_device.cpp).  This file adds what the C-ABI
+// promises around it:
+//   * a tail crypt (zrc4_crypt_host), a reseed or a state copy first drains
+//     every queued refill, then resets the slot or sets gen = pend = use;
+//   * a failed tail crypt loses its call's slots (ZRC4_ERR_STATE until
+//     reseeded or copied into);
+//   * a refill that cannot be queued is retried by the next call;
+//   * the fault latch is polled before a finished refill is committed;
 //   * every entry point takes the reservoir's mutex: one thread at a time per
 //     reservoir (and the context's staging buffers with it).
-// Same design as the session engine's reservoir hooks
-// (zsummerx_amd/engine/rc4_hooks_device.cpp), at the C-ABI so the mirror and
-// any other per-call user can have it.
 
 #include <mutex>
 
-namespace {
-
-template <class T>
-struct PinnedVec {
-    T *p = nullptr;
-    size_t cap = 0;
-    bool reserve(size_t n)
-    {
-        if (n <= cap) return true;
-        size_t c = cap ? cap : 1024;
-        while (c < n) c *= 2;
-        T *q = nullptr;
-        if (hipHostMalloc(reinterpret_cast<void **>(&q), c * sizeof(T), hipHostMallocCoherent) != hipSuccess)
-            return false;
-        if (p) (void)hipHostFree(p);
-        p = q;
-        cap = c;
-        return true;
-    }
-    void release()
-    {
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
-
-struct KsLevel {
-    uint64_t gen = 0, use = 0, pend = 0;
-    bool lost = false;    // a failed tail crypt: position unknown until reseeded or copied into
-};
-
-struct KsEntry {
-    uint32_t slot, len;
-    uint64_t off;
-};
-
-// A grouped batch (zrc4_crypt_grouped contract) in pinned tables.
-struct KsTable {
-    PinnedVec<uint32_t> ids, len;
-    PinnedVec<uint64_t> off;
-    std::vector<uint32_t> groups;   // each bucket's group (declared to the launch)
-    uint32_t n = 0;
-    bool build(std::vector<KsEntry> &es)
-    {
-        std::sort(es.begin(), es.end(), [](const KsEntry &a, const KsEntry &b) { return a.slot < b.slot; });
-        groups.clear();
-        for (size_t i = 0; i < es.size(); ++i)
-            if (!i || (es[i].slot >> 8) != (es[i - 1].slot >> 8)) groups.push_back(es[i].slot >> 8);
-        const uint32_t buckets = (uint32_t)groups.size();
-        n = buckets * zrc4::kGroup;
-        if (!ids.reserve(n) || !len.reserve(n) || !off.reserve(n)) return false;
-        for (uint32_t e = 0; e < n; ++e) {
-            ids.p[e] = ZRC4_IDLE_SLOT;
-            len.p[e] = 0;
-            off.p[e] = 0;
-        }
-        uint32_t b = 0, pos = 0;
-        for (size_t i = 0; i < es.size(); ++i) {
-            if (i && (es[i].slot >> 8) != (es[i - 1].slot >> 8)) {
-                ++b;
-                pos = 0;
-            }
-            const uint32_t e = b * zrc4::kGroup + pos++;
-            ids.p[e] = es[i].slot;
-            len.p[e] = es[i].len;
-            off.p[e] = es[i].off;
-        }
-        return true;
-    }
-    void release()
-    {
-        ids.release();
-        len.release();
-        off.release();
-    }
-};
-
-struct KsRefill {
-    KsTable t;
-    hipEvent_t ev = nullptr;
-    std::vector<std::pair<uint32_t, uint64_t>> ends;
-};
-
-}  // namespace
+#include "zrc4_reservoir.hpp"
 
 struct zrc4_ks {
-    static constexpr uint32_t kDepth = 2;
     zrc4_ctx *c = nullptr;
-    uint32_t ring = 0, chunk = 0;
     hipStream_t sB = nullptr;
     std::mutex mu;
-    std::vector<KsLevel> lv;
-    std::vector<uint8_t *> slab;          // per 256-slot group: 256 rings, allocated on first use
-    uint8_t *base = nullptr;              // offsets in refill tables are relative to the first slab
-    std::vector<uint8_t> hungryMark;
-    std::vector<uint32_t> hungry;
-    KsRefill rf[kDepth];
-    uint32_t head = 0, inflight = 0;
-    std::vector<KsEntry> es;
+    zrc4::Reservoir res;
+    std::vector<uint8_t> lost;            // a failed tail crypt: position unknown until reseeded or copied into
     std::vector<uint8_t> tailBuf;
     std::vector<uint32_t> tailIds, tailLen;
     std::vector<uint64_t> tailOff;
     std::vector<uint8_t *> tailDst;
-    uint64_t st[6] = {0, 0, 0, 0, 0, 0};  // ring bytes, tail bytes, tail launches, refill bytes, launches, waits
+    uint64_t tailBytes = 0, tailLaunches = 0;
     uint64_t refillFailures = 0;          // refills that could not be queued (retried by the next call)
     // Test hook, in ZRC4_TEST_HOOKS builds only (libzrc4_testhooks.so):
     // $ZRC4_KS_FAIL_TAIL_AFTER = n makes the n-th tail crypt of this reservoir
@@ -147,109 +45,29 @@ struct zrc4_ks {
     // its slots' positions -> ZRC4_ERR_STATE until reseeded).
     uint64_t failTailsAfter = 0, tailCalls = 0;
 
-    uint8_t *ringOf(uint32_t s)
+    auto faults()
     {
-        uint8_t *&sl = slab[s / zrc4::kGroup];
-        if (!sl) {
-            void *p = nullptr;
-            const size_t bytes = (size_t)zrc4::kGroup * ring;
-            if (hipHostMalloc(&p, bytes, hipHostMallocCoherent) != hipSuccess) return nullptr;
-            sl = static_cast<uint8_t *>(p);
-            if (!base) base = sl;
-        }
-        return sl + (size_t)(s % zrc4::kGroup) * ring;
+        return [this] { return zrc4_poll_faults(c); };
     }
+    int poll() { return res.poll(faults()); }
+    int drain() { return res.drain(faults()); }
 
-    int commitOldest(bool wait)
-    {
-        if (!inflight) return ZRC4_OK;
-        KsRefill &R = rf[head];
-        if (wait) {
-            ZRC4_TRY(hipEventSynchronize(R.ev));
-        } else {
-            const hipError_t q = hipEventQuery(R.ev);
-            if (q == hipErrorNotReady) return ZRC4_OK;
-            if (q != hipSuccess) return ZRC4_ERR_HIP;
-        }
-        const int rc = zrc4_poll_faults(c);
-        if (rc != ZRC4_OK) return rc;
-        for (const auto &e : R.ends) lv[e.first].gen = e.second;
-        head = (head + 1) % kDepth;
-        --inflight;
-        return ZRC4_OK;
-    }
-    int poll()
-    {
-        while (inflight) {
-            const uint32_t before = inflight;
-            const int rc = commitOldest(false);
-            if (rc != ZRC4_OK) return rc;
-            if (inflight == before) break;
-        }
-        return ZRC4_OK;
-    }
-    int drain()
-    {
-        while (inflight) {
-            const int rc = commitOldest(true);
-            if (rc != ZRC4_OK) return rc;
-        }
-        return ZRC4_OK;
-    }
-
-    // One write-only grouped launch into the rings' next free bytes of every
-    // hungry slot (whole chunks only: a launch lasts as long as its longest piece).
+    // One refill (zrc4_reservoir.hpp) as a write-only grouped launch, the path
+    // of zrc4_keystream_grouped.  (The groups built by the core are declared to
+    // the launch; trusted: no up-front check above 256 buckets, where they are
+    // not used.)
     int launchRefill()
     {
-        if (!ring || inflight >= kDepth || hungry.empty()) return ZRC4_OK;
-        KsRefill &R = rf[(head + inflight) % kDepth];
-        es.clear();
-        R.ends.clear();
-        for (uint32_t s : hungry)                 // rings first: no level moves if one cannot be had
-            if (!ringOf(s)) return ZRC4_ERR_OUT_OF_MEMORY;
-        std::vector<uint32_t> keep;
-        for (uint32_t s : hungry) {
-            KsLevel &L = lv[s];
-            if (ring - (L.pend - L.use) < chunk) {
-                hungryMark[s] = 0;
-                continue;
-            }
-            uint8_t *r = ringOf(s);
-            const uint32_t at = (uint32_t)(L.pend % ring);
-            const uint32_t amt = std::min(ring - at, chunk);
-            es.push_back({s, amt, (uint64_t)((uintptr_t)(r + at) - (uintptr_t)base)});
-            L.pend += amt;
-            R.ends.push_back({s, L.pend});
-            keep.push_back(s);
-            st[3] += amt;
-        }
-        hungry.swap(keep);
-        if (es.empty()) return ZRC4_OK;
-        // (the groups built here are declared to the launch; trusted: no
-        // up-front check above 256 buckets, where they are not used)
-        int rc = R.t.build(es) ? (set_device(c) ? ZRC4_ERR_HIP : ZRC4_OK) : ZRC4_ERR_OUT_OF_MEMORY;
-        if (rc == ZRC4_OK) {
-            CryptCall k = crypt_call(zrc4::kGrouped, R.t.ids.p, 0, base, R.t.off.p, R.t.len.p, R.t.n);
-            k.decl = R.t.groups.data();
-            k.trusted = true;
-            k.io = zrc4::kIoKs;
-            rc = launch_crypt(c, k, sB);
-        }
-        if (rc != ZRC4_OK) {                      // nothing queued: the levels go back
-            for (const KsEntry &e : es) lv[e.slot].pend -= e.len;
-            return rc;
-        }
-        ++st[4];
-        if (hipEventRecord(R.ev, sB) != hipSuccess) {
-            // queued but untrackable: wait for stream B and commit it now
-            ZRC4_TRY(hipStreamSynchronize(sB));
-            for (const auto &e : R.ends)
-                if (e.second > lv[e.first].gen) lv[e.first].gen = e.second;
-            R.ends.clear();
-            return zrc4_poll_faults(c);
-        }
-        ++inflight;
-        return ZRC4_OK;
+        return res.launchRefill(
+            [this](const zrc4::GroupedTable &t) {
+                if (set_device(c)) return ZRC4_ERR_HIP;
+                CryptCall k = crypt_call(zrc4::kGrouped, t.ids.p, 0, res.base, t.off.p, t.len.p, t.n);
+                k.decl = t.groups.data();
+                k.trusted = true;
+                k.io = zrc4::kIoKs;
+                return launch_crypt(c, k, sB);
+            },
+            faults());
     }
 
     // The device crypts the uncovered tails of a call (host spans), as one
@@ -264,12 +82,15 @@ struct zrc4_ks {
                              (uint32_t)tailIds.size());
         if (rc != ZRC4_OK) return rc;
         for (size_t i = 0; i < tailIds.size(); ++i) memcpy(tailDst[i], tailBuf.data() + tailOff[i], tailLen[i]);
-        ++st[2];
+        ++tailLaunches;
         return ZRC4_OK;
     }
 
-    // (the levels guard the ring bytes: what the ring still holds is never read)
-    void resetRing(uint32_t s) { lv[s] = KsLevel{}; }
+    void resetRing(uint32_t s)
+    {
+        res.reset(s);
+        lost[s] = 0;
+    }
 };
 
 extern "C" {
@@ -283,7 +104,6 @@ int zrc4_ks_create(zrc4_ctx *c, uint32_t ring_bytes, zrc4_ks **out)
     zrc4_ks *k = new (std::nothrow) zrc4_ks;
     if (!k) return ZRC4_ERR_OUT_OF_MEMORY;
     k->c = c;
-    k->ring = ring_bytes;
 #if defined(ZRC4_TEST_HOOKS) && ZRC4_TEST_HOOKS
     if (const char *f = getenv("ZRC4_KS_FAIL_TAIL_AFTER")) {
         k->failTailsAfter = strtoull(f, nullptr, 10);
@@ -294,13 +114,10 @@ int zrc4_ks_create(zrc4_ctx *c, uint32_t ring_bytes, zrc4_ks **out)
     // A quarter ring per refill: two refills stay queued while the consumer
     // keeps up (with half-ring chunks a slot had room for the next refill only
     // once the previous one was consumed, and the device idled between them).
-    k->chunk = ring_bytes ? std::max<uint32_t>(64u, ring_bytes / 4u) : 0u;
-    k->lv.resize(c->capacity);
-    k->slab.assign(c->capacity / zrc4::kGroup, nullptr);
-    k->hungryMark.assign(c->capacity, 0);
-    bool ok = hipStreamCreateWithFlags(&k->sB, hipStreamNonBlocking) == hipSuccess;
-    for (KsRefill &r : k->rf) ok = ok && hipEventCreateWithFlags(&r.ev, hipEventDisableTiming) == hipSuccess;
-    if (!ok) {
+    const uint32_t chunk = ring_bytes ? std::max<uint32_t>(64u, ring_bytes / 4u) : 0u;
+    k->lost.assign(c->capacity, 0);
+    if (hipStreamCreateWithFlags(&k->sB, hipStreamNonBlocking) != hipSuccess ||
+        k->res.init(c->capacity, ring_bytes, chunk, zrc4::Reservoir::kMaxDepth, k->sB, hipHostMallocCoherent) != ZRC4_OK) {
         zrc4_ks_destroy(k);
         return ZRC4_ERR_HIP;
     }
@@ -315,13 +132,8 @@ int zrc4_ks_destroy(zrc4_ks *k)
         std::lock_guard<std::mutex> g(k->mu);
         (void)k->drain();
         if (k->sB) (void)hipStreamSynchronize(k->sB);
-        for (KsRefill &r : k->rf) {
-            if (r.ev) (void)hipEventDestroy(r.ev);
-            r.t.release();
-        }
+        k->res.release();
         if (k->sB) (void)hipStreamDestroy(k->sB);
-        for (uint8_t *s : k->slab)
-            if (s) (void)hipHostFree(s);
     }
     delete k;
     return ZRC4_OK;
@@ -334,8 +146,8 @@ int zrc4_ks_crypt(zrc4_ks *k, const uint32_t *ids, uint8_t *const *data, const u
     for (uint32_t i = 0; i < n; ++i) {
         if (ids[i] >= k->c->capacity) return ZRC4_ERR_SLOT_RANGE;
         if (len[i] && !data[i]) return ZRC4_ERR_INVALID_ARG;
-        const KsLevel &L = k->lv[ids[i]];
-        if (L.lost || L.gen < L.use) return ZRC4_ERR_STATE;
+        const zrc4::Reservoir::Level &L = k->res.level(ids[i]);
+        if (k->lost[ids[i]] || L.gen < L.use) return ZRC4_ERR_STATE;
     }
     // a slot once per call (the keystream of a second span would be the first's)
     if (n > 1) {
@@ -347,18 +159,8 @@ int zrc4_ks_crypt(zrc4_ks *k, const uint32_t *ids, uint8_t *const *data, const u
     int rc = set_device(k->c);
     if (rc) return rc;
     if ((rc = k->poll()) != ZRC4_OK) return rc;
-    // A slot short of committed keystream while refills are queued: wait for
-    // them in order until it is covered or none is left.
-    for (;;) {
-        bool wait = false;
-        for (uint32_t i = 0; i < n && !wait; ++i) {
-            const KsLevel &L = k->lv[ids[i]];
-            if (L.gen - L.use < len[i] && L.pend > L.gen) wait = true;
-        }
-        if (!wait || !k->inflight) break;
-        ++k->st[5];
-        if ((rc = k->commitOldest(true)) != ZRC4_OK) return rc;
-    }
+    rc = k->res.waitCovered(n, [&](uint32_t i) { return std::pair<uint32_t, uint32_t>(ids[i], len[i]); }, k->faults());
+    if (rc != ZRC4_OK) return rc;
     k->tailIds.clear();
     k->tailLen.clear();
     k->tailOff.clear();
@@ -367,34 +169,20 @@ int zrc4_ks_crypt(zrc4_ks *k, const uint32_t *ids, uint8_t *const *data, const u
     for (uint32_t i = 0; i < n; ++i) {
         const uint32_t s = ids[i];
         if (!len[i]) continue;
-        KsLevel &L = k->lv[s];
-        const uint32_t have = (uint32_t)std::min<uint64_t>(L.gen - L.use, len[i]);
-        if (have) {
-            uint8_t *r = k->ringOf(s);
-            uint32_t done = 0;
-            while (done < have) {
-                const uint32_t at = (uint32_t)((L.use + done) % k->ring);
-                const uint32_t m = std::min(have - done, k->ring - at);
-                uint8_t *d = data[i] + done, *q = r + at;
-                for (uint32_t b = 0; b < m; ++b) d[b] ^= q[b];
-                done += m;
-            }
-            L.use += have;
-            k->st[0] += have;
-        }
-        if (have < len[i]) {
-            const uint32_t t = len[i] - have;
+        const uint32_t t = k->res.cover(s, len[i], [&](uint32_t done, const uint8_t *q, uint32_t m) {
+            uint8_t *d = data[i] + done;
+            for (uint32_t b = 0; b < m; ++b) d[b] ^= q[b];
+        });
+        if (t) {
+            const uint32_t have = len[i] - t;
             k->tailIds.push_back(s);
             k->tailLen.push_back(t);
             k->tailOff.push_back(k->tailBuf.size());
             k->tailDst.push_back(data[i] + have);
             k->tailBuf.insert(k->tailBuf.end(), data[i] + have, data[i] + len[i]);
-            k->st[1] += t;                       // use moves only once the tail crypt succeeded
+            k->tailBytes += t;                   // use moves only once the tail crypt succeeded
         }
-        if (k->ring && !k->hungryMark[s]) {
-            k->hungryMark[s] = 1;
-            k->hungry.push_back(s);
-        }
+        k->res.markHungry(s);
     }
     if (!k->tailIds.empty()) {
         if ((rc = k->runTails()) != ZRC4_OK) {
@@ -404,26 +192,22 @@ int zrc4_ks_crypt(zrc4_ks *k, const uint32_t *ids, uint8_t *const *data, const u
             // on later calls) until reseeded or copied into -- a caller
             // cannot retry part of a batch it cannot see.
             for (uint32_t i = 0; i < n; ++i)
-                if (len[i]) k->lv[ids[i]].lost = true;
+                if (len[i]) k->lost[ids[i]] = 1;
             return rc;
         }
-        for (size_t t = 0; t < k->tailIds.size(); ++t) {
-            KsLevel &L = k->lv[k->tailIds[t]];
-            L.use += k->tailLen[t];
-            L.gen = L.pend = L.use;
-        }
+        for (size_t t = 0; t < k->tailIds.size(); ++t) k->res.afterTail(k->tailIds[t], k->tailLen[t]);
     }
     // Background refills are best-effort for this call: its bytes are already
     // crypted, so a refill that cannot be queued now (pinned-memory or launch
     // failure) is retried by the next call, which crypts on the device what
     // the rings then lack.  Hard errors are reserved for the tail path.
-    while (k->inflight < zrc4_ks::kDepth) {
-        const uint32_t before = k->inflight;
+    while (k->res.inflight() < zrc4::Reservoir::kMaxDepth) {
+        const uint32_t before = k->res.inflight();
         if (k->launchRefill() != ZRC4_OK) {
             ++k->refillFailures;
             break;
         }
-        if (k->inflight == before) break;
+        if (k->res.inflight() == before) break;
     }
     return ZRC4_OK;
 }
@@ -454,10 +238,10 @@ int zrc4_ks_copy(zrc4_ks *dk, uint32_t dst, zrc4_ks *sk, uint32_t src)
     int rc;
     if ((rc = sk->drain()) != ZRC4_OK) return rc;
     if (dk != sk && (rc = dk->drain()) != ZRC4_OK) return rc;
-    const KsLevel S = sk->lv[src];
-    if (S.lost) return ZRC4_ERR_STATE;
+    const zrc4::Reservoir::Level S = sk->res.level(src);
+    if (sk->lost[src]) return ZRC4_ERR_STATE;
     const uint64_t buffered = S.gen - S.use;
-    if (buffered > dk->ring) return ZRC4_ERR_INVALID_ARG;
+    if (buffered > dk->res.ring()) return ZRC4_ERR_INVALID_ARG;
     if (dk->c->device == sk->c->device) {
         // the state at S.gen, slot to slot on the device: two launches, one wait
         if ((rc = zrc4_copy_states(dk->c, nullptr, dst, sk->c, nullptr, src, 1, dk->c->stream)) != ZRC4_OK) return rc;
@@ -471,10 +255,10 @@ int zrc4_ks_copy(zrc4_ks *dk, uint32_t dst, zrc4_ks *sk, uint32_t src)
     }
     dk->resetRing(dst);
     if (buffered) {
-        uint8_t *sr = sk->ringOf(src), *dr = dk->ringOf(dst);
+        uint8_t *sr = sk->res.ringOf(src), *dr = dk->res.ringOf(dst);
         if (!sr || !dr) return ZRC4_ERR_OUT_OF_MEMORY;
-        for (uint64_t i = 0; i < buffered; ++i) dr[i] = sr[(S.use + i) % sk->ring];
-        dk->lv[dst].gen = dk->lv[dst].pend = buffered;
+        for (uint64_t i = 0; i < buffered; ++i) dr[i] = sr[(S.use + i) % sk->res.ring()];
+        dk->res.reset(dst, buffered);
     }
     return ZRC4_OK;
 }
@@ -483,7 +267,10 @@ int zrc4_ks_stats(zrc4_ks *k, uint64_t out[6])
 {
     if (!k || !out) return ZRC4_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> g(k->mu);
-    for (int i = 0; i < 6; ++i) out[i] = k->st[i];
+    // ring bytes, tail bytes, tail launches, refill bytes (queued), refill launches, refill waits
+    const uint64_t st[6] = {k->res.coveredBytes, k->tailBytes, k->tailLaunches,
+                            k->res.queuedBytes, k->res.launches, k->res.waits};
+    for (int i = 0; i < 6; ++i) out[i] = st[i];
     return ZRC4_OK;
 }
 

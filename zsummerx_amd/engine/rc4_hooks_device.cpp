@@ -21,32 +21,24 @@
 //              themselves, then a wait.  A span's latency is its serial RC4
 //              chain: ~40 ns per byte on one lane (rc4_encryption.h:83-88 is
 //              byte-serial), so small batches wait on the chain.
-//   reservoir  (default) RC4's keystream does not depend on the data, so each
-//              slot's keystream is generated AHEAD by the GPU -- a background
-//              stream runs zrc4_keystream_grouped, which STORES the slot's
-//              next keystream bytes and never reads the ring -- into a ring
-//              of `ring` bytes in PINNED HOST memory (written over PCIe by
-//              the kernel; nothing crosses the link the other way, and the
-//              host never zeroes a ring byte).  The hook then XORs each
-//              span with committed ring bytes on the host: no GPU round trip
-//              on the latency path.  Only a slot whose committed keystream
-//              does not cover its span goes to the GPU synchronously, and only
-//              for the missing tail (the slot's state sits exactly at the end
-//              of its committed keystream).  The RC4 state never leaves the
-//              device; keystream bytes are consumed strictly in order, so the
-//              wire bytes are the reference's.
-// Ordering rules (streams: A = synchronous work, B = background refill):
-//   * the host reads only ring bytes of COMMITTED refills (their event has
-//     completed) that it has not consumed yet; a refill writes only ring
-//     bytes past the committed end -- the two never touch the same bytes.
-//     The levels (Level) alone say which ring bytes hold keystream: consumed
-//     bytes, a reseeded slot's dropped ones and a fresh slab's contents stay
-//     as they are until a refill overwrites them, and are never read
-//     ($ZSX_RING_POISON=1 fills fresh slabs with 0xA5 to show it);
-//   * kernels that touch slot state (ksa, tail crypt, refill) never run on A
-//     and B at once: a grouped kernel stores its whole group image, so A
-//     waits for every queued refill on B before a seed or a tail crypt;
-//   * refills on B run in stream order, at most kRefillDepth queued.
+//   reservoir  (default) each slot's keystream is generated AHEAD by the GPU
+//              -- a background stream runs zrc4_keystream_grouped -- into a
+//              ring of `ring` bytes in PINNED HOST memory (written over PCIe
+//              by the kernel; nothing crosses the link the other way).  The
+//              hook XORs each span with committed ring bytes on the host: no
+//              GPU round trip on the latency path.  Only the tail of a span
+//              that its slot's committed keystream does not cover goes to the
+//              GPU synchronously.  The wire bytes are the reference's.
+// The levels, rings, hungry list and refill queue are the reservoir core's
+// (csrc/zrc4_reservoir.hpp, shared with the C-ABI reservoir zrc4_ks_*): its
+// header states the design and its invariants.  What the hooks add (streams:
+// A = synchronous work, B = background refill):
+//   * kernels that touch slot state never run on A and B at once: A waits
+//     for every queued refill on B before a seed (flushSeeds) or a tail crypt;
+//   * the adaptive switch to direct launches (updateMode), the host XOR spread
+//     over worker threads (XorPool), the ZSX_* knobs ($ZSX_RING_POISON=1 fills
+//     fresh ring slabs with 0xA5) and stats();
+//   * the fault latch is polled once after every batch of committed refills.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -63,6 +55,7 @@
 #include <vector>
 
 #include "zrc4.h"
+#include "zrc4_reservoir.hpp"
 #include "zsummerx_amd/rc4_hooks.h"
 
 namespace zsummerx_amd {
@@ -89,55 +82,16 @@ unsigned hostAllocFlags()
     return f;
 }
 
+// Out of pinned memory is std::bad_alloc here.
 template <class T>
-struct PinnedArray {
-    T *p = nullptr;
-    size_t cap = 0;
+struct PinnedArray : zrc4::Pinned<T> {
     void reserve(size_t n)
     {
-        if (n <= cap) return;
-        size_t c = cap ? cap : 1024;
-        while (c < n) c *= 2;
-        T *q = nullptr;
-        if (hipHostMalloc(reinterpret_cast<void **>(&q), c * sizeof(T), hostAllocFlags()) != hipSuccess)
-            throw std::bad_alloc();
-        if (p) {
-            std::memcpy(q, p, cap * sizeof(T));   // keep the entries already pushed
-            (void)hipHostFree(p);
-        }
-        p = q;
-        cap = c;
-    }
-    ~PinnedArray()
-    {
-        if (p) (void)hipHostFree(p);
+        if (!zrc4::Pinned<T>::reserve(n, hostAllocFlags())) throw std::bad_alloc();
     }
 };
 
-// One grouped batch table (ids / offsets / lengths) in pinned memory.
-struct Table {
-    PinnedArray<uint32_t> ids, len;
-    PinnedArray<uint64_t> off;
-    std::vector<uint32_t> groups;   // each bucket's group, declared to zrc4_crypt_grouped_declared
-    uint32_t n = 0;
-    void clear()
-    {
-        n = 0;
-        groups.clear();
-    }
-    void push(uint32_t id, uint64_t o, uint32_t l)
-    {
-        if (n == ids.cap || n == off.cap || n == len.cap) {
-            ids.reserve(n + 1);
-            off.reserve(n + 1);
-            len.reserve(n + 1);
-        }
-        ids.p[n] = id;
-        off.p[n] = o;
-        len.p[n] = l;
-        ++n;
-    }
-};
+using Table = zrc4::GroupedTable;   // one grouped batch table (ids / offsets / lengths) in pinned memory
 
 // A grouped launch over table t: the groups built here are declared with it
 // up to 256 buckets, where the kernels take them in their arguments and load
@@ -185,48 +139,21 @@ struct FrameTable {
     }
 };
 
-// zrc4_crypt_grouped layout: entries sorted by slot, a new 256-entry bucket
-// at every group change (each group holds at most 256 distinct slots, so one
-// bucket per group).
+// The grouped layout of the core's builder over `es`, with the per-entry
+// framing tables of a framed launch riding on it.
 void buildGrouped(Table &t, std::vector<Entry> &es, FrameTable *ft = nullptr)
 {
-    std::sort(es.begin(), es.end(), [](const Entry &a, const Entry &b) { return a.slot < b.slot; });
-    t.clear();
     if (ft) ft->idx.clear();
-    auto push = [&](uint32_t slot, uint64_t off, uint32_t len, const Entry *e) {
-        t.push(slot, off, len);
+    const bool ok = zrc4::buildGrouped(t, es, [&](const Entry *e) {
         if (ft) {
             ft->reserve(t.n);
             ft->off.p[t.n - 1] = e ? e->foff : 0;
             ft->len.p[t.n - 1] = e ? e->flen : 0;
             ft->idx.push_back(e ? (int64_t)e->idx : -1);
         }
-    };
-    uint32_t cur = ZRC4_IDLE_SLOT;
-    for (const Entry &e : es) {
-        const uint32_t g = e.slot >> 8;
-        if (g != cur) {
-            while (t.n % ZRC4_GROUP_SLOTS) push(ZRC4_IDLE_SLOT, 0, 0, nullptr);
-            cur = g;
-            t.groups.push_back(g);
-        }
-        push(e.slot, e.off, e.len, &e);
-    }
+    });
+    if (!ok) throw std::bad_alloc();
 }
-
-struct Level {
-    uint64_t gen = 0;    // keystream bytes generated and committed (absolute stream position)
-    uint64_t use = 0;    // keystream bytes consumed
-    uint64_t pend = 0;   // end of the last queued refill (== gen when none is in flight)
-};
-
-// One background refill launch: its grouped table, its completion event and
-// the (slot, end position) pairs it commits.
-struct Refill {
-    Table t;
-    hipEvent_t ev = nullptr;
-    std::vector<std::pair<uint32_t, uint64_t>> ends;
-};
 
 // dst ^= src for n bytes (word-wise where possible).
 void xorBytes(uint8_t *__restrict dst, const uint8_t *__restrict src, size_t n)
@@ -351,22 +278,21 @@ public:
         bool ok = hipSetDevice(device) == hipSuccess &&
                   hipStreamCreateWithFlags(&sA_, hipStreamNonBlocking) == hipSuccess &&
                   hipStreamCreateWithFlags(&sB_, hipStreamNonBlocking) == hipSuccess;
-        for (Refill &r : refill_) ok = ok && hipEventCreateWithFlags(&r.ev, hipEventDisableTiming) == hipSuccess;
-        if (!ok) {
-            release();
-            throw std::runtime_error("makeDeviceRc4Hooks: HIP stream/event creation failed");
-        }
-        seen_.assign(zrc4_capacity(ctx_), 0u);
-        if (ringCap_) {
-            level_.resize(zrc4_capacity(ctx_));
-            ringSlab_.assign(zrc4_capacity(ctx_) / ZRC4_GROUP_SLOTS, nullptr);
-            hungryMark_.assign(zrc4_capacity(ctx_), 0u);
+        tt_.flags = hostAllocFlags();
+        if (ok && ringCap_) {
             // $ZSX_REFILL_CHUNK (A/B knob): bytes per slot per refill, at most a
             // quarter of the ring (two refills in flight leave half of it readable)
             const char *rc = std::getenv("ZSX_REFILL_CHUNK");
             const uint32_t want = rc ? (uint32_t)std::strtoul(rc, nullptr, 10) : kRefillChunk;
             refillChunk_ = std::max<uint32_t>(256u, std::min<uint32_t>(want, ringCap_ / 4));
+            ok = res_.init(zrc4_capacity(ctx_), ringCap_, refillChunk_, refillDepth_, sB_, hostAllocFlags(),
+                           ringPoison_ ? 0xA5 : -1) == ZRC4_OK;
         }
+        if (!ok) {
+            release();
+            throw std::runtime_error("makeDeviceRc4Hooks: HIP stream/event creation failed");
+        }
+        seen_.assign(zrc4_capacity(ctx_), 0u);
     }
     ~DeviceRc4Hooks() override { release(); }
 
@@ -377,7 +303,7 @@ public:
     {
         void *p = nullptr;
         if (hipHostMalloc(&p, bytes, hostAllocFlags()) != hipSuccess) throw std::bad_alloc();
-        if (!base_) base_ = static_cast<uint8_t *>(p);
+        if (!res_.base) res_.base = static_cast<uint8_t *>(p);
         return p;
     }
     void freeBlocks(void *p) override
@@ -448,7 +374,7 @@ public:
         buildGrouped(tt_, es_, &ft_);
         zrc4_frame_args fa{ft_.off.p, ft_.len.p, bound, Rc4Frame::kMaxPackets, ft_.npk.p, ft_.used.p,
                            ft_.status.p, ft_.pkt.p};
-        rc = launchGrouped(ctx_, tt_, base_, &fa, sA_);
+        rc = launchGrouped(ctx_, tt_, res_.base, &fa, sA_);
         if (rc != ZRC4_OK) return rc;
         ++tailLaunches_;
         if ((rc = zrc4_sync(ctx_, sA_)) != ZRC4_OK) return rc;
@@ -474,34 +400,18 @@ public:
                       "\"refill_bytes\": %llu, \"refill_launches\": %llu, \"refill_waits\": %llu, "
                       "\"ring_cap\": %u, \"refill_chunk\": %u, \"device_framed\": %llu, \"xor_threads\": %u, "
                       "\"direct_calls\": %llu, \"direct_bytes\": %llu, \"keystream_launches\": %llu}",
-                      ringBytes_, tailBytes_, tailLaunches_, refillBytes_, refillLaunches_, refillWaits_, ringCap_,
-                      refillChunk_, framed_, xor_.threads(), directCalls_, (unsigned long long)directBytes_,
-                      keystreamLaunches_);
+                      (unsigned long long)res_.coveredBytes, tailBytes_, tailLaunches_,
+                      (unsigned long long)res_.committedBytes, (unsigned long long)res_.launches,
+                      (unsigned long long)res_.waits, ringCap_, refillChunk_, framed_, xor_.threads(), directCalls_,
+                      (unsigned long long)directBytes_, (unsigned long long)res_.launches);   // (every refill is a keystream launch)
         return b;
     }
 
 private:
     uint64_t offOf(const void *p)
     {
-        if (!base_) base_ = static_cast<uint8_t *>(const_cast<void *>(p));
-        return (uint64_t)((uintptr_t)p - (uintptr_t)base_);
-    }
-
-    // The ring of slot s: pinned host memory, one slab of 256 rings per group,
-    // allocated on first use and left as it comes (refills store into it and
-    // the levels guard what is read; $ZSX_RING_POISON=1, a test knob, fills it
-    // with 0xA5 so that a byte read outside the levels cannot pass for zero).
-    uint8_t *ringOf(uint32_t s)
-    {
-        uint8_t *&slab = ringSlab_[s / ZRC4_GROUP_SLOTS];
-        if (!slab) {
-            const size_t bytes = (size_t)ZRC4_GROUP_SLOTS * ringCap_;
-            void *p = nullptr;
-            if (hipHostMalloc(&p, bytes, hostAllocFlags()) != hipSuccess) throw std::bad_alloc();
-            if (ringPoison_) std::memset(p, 0xA5, bytes);
-            slab = static_cast<uint8_t *>(p);
-        }
-        return slab + (size_t)(s % ZRC4_GROUP_SLOTS) * ringCap_;
+        if (!res_.base) res_.base = static_cast<uint8_t *>(const_cast<void *>(p));
+        return (uint64_t)((uintptr_t)p - (uintptr_t)res_.base);
     }
 
     // One grouped launch on A over `es`, then the wait.
@@ -509,7 +419,7 @@ private:
     {
         if (es.empty()) return ZRC4_OK;
         buildGrouped(tt_, es);
-        int rc = launchGrouped(ctx_, tt_, base_, nullptr, sA_);
+        int rc = launchGrouped(ctx_, tt_, res_.base, nullptr, sA_);
         if (rc != ZRC4_OK) return rc;
         ++tailLaunches_;
         return zrc4_sync(ctx_, sA_);
@@ -551,19 +461,9 @@ private:
         updateMode(spans, n);
         int rc = pollRefills(false);
         if (rc != ZRC4_OK) return rc;
-        // A slot short of committed keystream while refills are queued: wait
-        // for them in order until it is covered or none is left (their bytes
-        // are the ones it needs, and a tail crypt may not run beside them).
-        for (;;) {
-            bool wait = false;
-            for (uint32_t i = 0; i < n && !wait; ++i) {
-                const Level &L = level_[spans[i].slot];
-                if (L.gen - L.use < spans[i].len && L.pend > L.gen) wait = true;
-            }
-            if (!wait || !inFlight_) break;      // nothing queued: the span goes to the tail path
-            ++refillWaits_;
-            if ((rc = commitOldest(true)) != ZRC4_OK) return rc;
-        }
+        rc = res_.waitCovered(n, [&](uint32_t i) { return std::pair<uint32_t, uint32_t>(spans[i].slot, spans[i].len); },
+                              zrc4::NoFaults());
+        if (rc != ZRC4_OK) return rc;
         // Host XOR with the committed ring bytes (XorPool, after this pass:
         // before any refill is launched, since a refill may write the ring
         // bytes consumed here); collect the uncovered tails.
@@ -573,150 +473,54 @@ private:
         for (uint32_t i = 0; i < n; ++i) {
             const Rc4Span &sp = spans[i];
             if (!sp.len) continue;
-            Level &L = level_[sp.slot];
-            const uint32_t have = (uint32_t)std::min<uint64_t>(L.gen - L.use, sp.len);
-            if (have) {
-                uint8_t *r = ringOf(sp.slot);
-                uint32_t done = 0;
-                while (done < have) {
-                    const uint32_t at = (uint32_t)((L.use + done) % ringCap_);
-                    const uint32_t k = std::min(have - done, ringCap_ - at);
-                    xj_.push_back({sp.data + done, r + at, k});
-                    done += k;
-                }
-                L.use += have;
-                ringBytes_ += have;
-                xjBytes += have;
+            const uint32_t tail = res_.cover(sp.slot, sp.len, [&](uint32_t done, const uint8_t *q, uint32_t k) {
+                xj_.push_back({sp.data + done, q, k});
+            });
+            xjBytes += sp.len - tail;
+            if (tail) {
+                // the slot's device state is at the end of what the ring covered
+                es_.push_back({sp.slot, tail, offOf(sp.data + (sp.len - tail))});
+                res_.afterTail(sp.slot, tail);
+                tailBytes_ += tail;
             }
-            if (have < sp.len) {
-                // the slot's device state is at position L.gen == L.use
-                es_.push_back({sp.slot, sp.len - have, offOf(sp.data + have)});
-                L.use += sp.len - have;
-                L.gen = L.pend = L.use;
-                tailBytes_ += sp.len - have;
-            }
-            if (!direct_ && !hungryMark_[sp.slot]) {
-                hungryMark_[sp.slot] = 1;
-                hungry_.push_back(sp.slot);
-            }
+            if (!direct_) res_.markHungry(sp.slot);
         }
         xor_.run(xj_, xjBytes);
         if (!es_.empty()) {
             if ((rc = drainRefills()) != ZRC4_OK) return rc;     // slot state must be quiet
             if ((rc = runTail(es_)) != ZRC4_OK) return rc;
         }
-        while (!direct_ && inFlight_ < refillDepth_) {
-            const uint32_t before = inFlight_;
+        while (!direct_ && !debugNoRefill_ && res_.inflight() < refillDepth_) {
+            const uint32_t before = res_.inflight();
             if ((rc = launchRefill()) != ZRC4_OK) return rc;
-            if (inFlight_ == before) break;
+            if (res_.inflight() == before) break;
         }
         return ZRC4_OK;
     }
 
-    // Background refill of the slots used since the last one, each up to a
-    // full ring (counting what is already queued), in one piece of at most
-    // refillChunk_ bytes per slot (one chunk's chain ~ refillChunk_ x 40 ns),
-    // written straight into the pinned host rings.  Up to kRefillDepth
-    // refills are queued back to back on stream B, so a stream's keystream
-    // generation does not pause between launches (stream order keeps each
-    // slot's pieces sequential).
+    // One background refill (zrc4_reservoir.hpp) as a zrc4_keystream_grouped
+    // launch on B, written straight into the pinned host rings: one chunk's
+    // chain ~ refillChunk_ x 40 ns.
     int launchRefill()
     {
-        if (inFlight_ >= refillDepth_ || debugNoRefill_ || hungry_.empty()) return ZRC4_OK;
-        Refill &R = refill_[(head_ + inFlight_) % kRefillDepth];
-        rs_.clear();
-        R.ends.clear();
-        std::vector<uint32_t> keep;
-        for (uint32_t s : hungry_) {
-            Level &L = level_[s];
-            const uint64_t level = L.pend - L.use;
-            // Whole chunks only: a launch lasts as long as its longest piece
-            // (one lane per slot), so every slot it carries gets a full chunk
-            // (or the piece up to the ring end).  A slot without room for one
-            // leaves the hungry list until it is consumed from again.
-            if (ringCap_ - level < refillChunk_) {
-                hungryMark_[s] = 0;
-                continue;
-            }
-            const uint32_t at = (uint32_t)(L.pend % ringCap_);
-            const uint32_t amt = std::min(ringCap_ - at, refillChunk_);
-            rs_.push_back({s, amt, offOf(ringOf(s) + at)});
-            L.pend += amt;
-            R.ends.push_back({s, L.pend});
-            keep.push_back(s);                      // re-examined at the next launch
-        }
-        hungry_.swap(keep);
-        if (rs_.empty()) return ZRC4_OK;
-        buildGrouped(R.t, rs_);
-        int rc = launchKeystream(ctx_, R.t, base_, sB_);
-        if (rc != ZRC4_OK) {
-            // nothing queued: the levels go back (pend > gen with no refill in
-            // flight would make cryptReservoir wait for bytes that never come)
-            for (const Entry &e : rs_) level_[e.slot].pend -= e.len;
-            R.ends.clear();
-            return rc;
-        }
-        ++refillLaunches_;
-        ++keystreamLaunches_;
-        if (hipEventRecord(R.ev, sB_) != hipSuccess) {
-            // the refill is queued but cannot be tracked: wait for stream B
-            // and commit its bytes now
-            if (hipStreamSynchronize(sB_) != hipSuccess) return ZRC4_ERR_HIP;
-            for (const auto &se : R.ends) {
-                Level &L = level_[se.first];
-                if (se.second > L.gen) {
-                    refillBytes_ += se.second - L.gen;
-                    L.gen = se.second;
-                }
-            }
-            R.ends.clear();
-            return zrc4_poll_faults(ctx_);
-        }
-        ++inFlight_;
-        if (debugSyncRefill_) return drainRefills();
-        return ZRC4_OK;
-    }
-
-    // Commit the oldest queued refill if it has finished (wait = block until
-    // it has).  Refills complete in stream order.
-    int commitOldest(bool wait)
-    {
-        if (!inFlight_) return ZRC4_OK;
-        Refill &R = refill_[head_];
-        if (wait) {
-            if (hipEventSynchronize(R.ev) != hipSuccess) return ZRC4_ERR_HIP;
-        } else {
-            const hipError_t q = hipEventQuery(R.ev);
-            if (q == hipErrorNotReady) return ZRC4_ERR_NOT_READY_;
-            if (q != hipSuccess) return ZRC4_ERR_HIP;
-        }
-        for (const auto &se : R.ends) {
-            Level &L = level_[se.first];
-            if (se.second > L.gen) {
-                refillBytes_ += se.second - L.gen;
-                L.gen = se.second;
-            }
-        }
-        R.ends.clear();
-        head_ = (head_ + 1) % kRefillDepth;
-        --inFlight_;
-        return ZRC4_OK;
+        const uint32_t before = res_.inflight();
+        const int rc = res_.launchRefill([this](const Table &t) { return launchKeystream(ctx_, t, res_.base, sB_); },
+                                         [this] { return zrc4_poll_faults(ctx_); });
+        if (rc == ZRC4_ERR_OUT_OF_MEMORY) throw std::bad_alloc();   // pinned memory: a ring slab or a table
+        if (rc == ZRC4_OK && debugSyncRefill_ && res_.inflight() != before) return drainRefills();
+        return rc;
     }
 
     // Commit every finished refill (wait = every queued one), then report
-    // latched device faults of stream B.
+    // latched device faults of stream B: committed refills have completed, so
+    // their faults are in the latch (no stream wait -- a second queued refill
+    // keeps running).
     int pollRefills(bool wait)
     {
-        bool any = false;
-        while (inFlight_) {
-            const int rc = commitOldest(wait);
-            if (rc == ZRC4_ERR_NOT_READY_) break;
-            if (rc != ZRC4_OK) return rc;
-            any = true;
-        }
-        // committed refills have completed: their faults are in the latch
-        // (no stream wait -- a second queued refill keeps running)
-        return any ? zrc4_poll_faults(ctx_) : ZRC4_OK;
+        const uint64_t before = res_.commits;
+        const int rc = wait ? res_.drain(zrc4::NoFaults()) : res_.poll(zrc4::NoFaults());
+        if (rc != ZRC4_OK) return rc;
+        return res_.commits != before ? zrc4_poll_faults(ctx_) : ZRC4_OK;
     }
     int drainRefills() { return pollRefills(true); }
 
@@ -730,7 +534,7 @@ private:
         int rc;
         if (ringCap_) {
             if ((rc = drainRefills()) != ZRC4_OK) return rc;
-            for (uint32_t s : seedIds_) level_[s] = Level();
+            for (uint32_t s : seedIds_) res_.reset(s);
         } else if ((rc = zrc4_sync(ctx_, sA_)) != ZRC4_OK) {
             return rc;
         }
@@ -757,18 +561,9 @@ private:
     {
         if (sB_) (void)hipStreamSynchronize(sB_);
         if (sA_) (void)hipStreamSynchronize(sA_);
-        for (Refill &r : refill_)
-            if (r.ev) {
-                (void)hipEventDestroy(r.ev);
-                r.ev = nullptr;
-            }
+        res_.release();
         if (sA_) (void)hipStreamDestroy(sA_);
         if (sB_) (void)hipStreamDestroy(sB_);
-        for (uint8_t *&slab : ringSlab_)
-            if (slab) {
-                (void)hipHostFree(slab);
-                slab = nullptr;
-            }
         if (ctx_) zrc4_destroy(ctx_);
         sA_ = sB_ = nullptr;
         ctx_ = nullptr;
@@ -779,9 +574,7 @@ private:
     // few-session engine is bound by that chain (config 1: 113.3k -> 117.0k
     // echo/s, scripts/r06_refill_ab.sh)
     static constexpr uint32_t kRefillChunk = 16384;
-    static constexpr uint32_t kRefillDepth = 2;
-    const uint32_t refillDepth_ = std::getenv("ZSX_REFILL_DEPTH") ? std::max(1, std::min(2, std::atoi(std::getenv("ZSX_REFILL_DEPTH")))) : kRefillDepth;
-    static constexpr int ZRC4_ERR_NOT_READY_ = 1;   // internal: oldest refill still running
+    const uint32_t refillDepth_ = std::getenv("ZSX_REFILL_DEPTH") ? std::max(1, std::min(2, std::atoi(std::getenv("ZSX_REFILL_DEPTH")))) : zrc4::Reservoir::kMaxDepth;
     const uint64_t directBytes_ = std::getenv("ZSX_RC4_DIRECT_BYTES")
                                      ? std::strtoull(std::getenv("ZSX_RC4_DIRECT_BYTES"), nullptr, 10)
                                      : (1ull << 20);
@@ -794,20 +587,14 @@ private:
 
     zrc4_ctx *ctx_ = nullptr;
     hipStream_t sA_ = nullptr, sB_ = nullptr;
-    Refill refill_[kRefillDepth];
-    uint32_t head_ = 0, inFlight_ = 0;
-    uint8_t *base_ = nullptr;
+    zrc4::Reservoir res_;                         // (its base is the payload base of every launch here)
     uint32_t ringCap_;
     uint32_t refillChunk_ = 0;
-    std::vector<uint8_t *> ringSlab_;
-    std::vector<Level> level_;
     std::vector<uint32_t> seen_;
     uint32_t callStamp_ = 0;
-    std::vector<uint8_t> hungryMark_;
-    std::vector<uint32_t> hungry_;
     std::vector<XorJob> xj_;
     XorPool xor_;
-    std::vector<Entry> es_, rs_;
+    std::vector<Entry> es_;
     Table tt_;                                    // tail grouped table
     FrameTable ft_;                               // framing tables of cryptFrame
     PinnedArray<uint32_t> kIds_, kLen_;
@@ -816,8 +603,7 @@ private:
     std::vector<uint32_t> seedIds_, seedLen_;
     std::vector<uint64_t> seedOff_;
     std::vector<uint8_t> keyBytes_;
-    unsigned long long ringBytes_ = 0, tailBytes_ = 0, tailLaunches_ = 0, refillBytes_ = 0, refillLaunches_ = 0,
-                       refillWaits_ = 0, framed_ = 0, keystreamLaunches_ = 0;
+    unsigned long long tailBytes_ = 0, tailLaunches_ = 0, framed_ = 0;
 };
 
 }  // namespace
