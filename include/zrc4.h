@@ -192,6 +192,10 @@ int zrc4_crypt_grouped_declared(zrc4_ctx *ctx, const uint32_t *ids,
  *     an id >= capacity, reported as ZRC4_ERR_SLOT_RANGE) is left untouched;
  *   - the spans of a bucket refused with ZRC4_ERR_GROUP are unspecified:
  *     untouched or zero.  Its slots' states are untouched.
+ *   - launches of at most one group or bucket per CU leave a refused bucket's
+ *     spans untouched: the kernels return, or lose their claim, before their
+ *     first store, as in the in-place calls (zero shows only behind the
+ *     zeroing launch below).
  * `out` is device memory or coherent pinned host memory, at any alignment
  * (16-byte aligned span starts store whole 16-byte units).  With at most one
  * group or bucket per CU the kernels store the keystream themselves, in one
@@ -309,7 +313,11 @@ int zrc4_crypt_to_grouped(zrc4_ctx *ctx, const uint32_t *ids, const uint32_t *bu
  * successive two-launch zrc4_crypt_to_* sequences on `stream` from a host
  * loop: nothing is saved over separate calls, the claims are taken PER ROUND
  * (two buckets naming one group may split differently in different rounds),
- * and each slot is all-or-nothing per round, not per call.
+ * and each slot is all-or-nothing per round, not per call.  Every round is
+ * there JUDGED as a one-round call, by that round's lengths: a slot named a
+ * second time with length 0 is allowed and its bucket runs, and a bucket whose
+ * lengths are all zero is idle in that round (declared idle or not, it is not
+ * refused), where the one-launch call above refuses both.
  * Device pointers apart from bucket_group; asynchronous. */
 #define ZRC4_MAX_ROUNDS 64u
 int
