@@ -8,9 +8,11 @@
 //   plan_check classes   the family of every in-place, undeclared range and
 //                        grouped shape of the sweep, one per line:
 //                        mode first_aligned G cus frame family
+//                        (tests/test_crypt_plan.py: kernel_class of
+//                        tests/dispatch_model.py says the same)
 //   plan_check plan ...  the plan of each shape given on the command line
-//                        (tests/test_gpu_addressing.py checks its own statement
-//                        of the family against it)
+//                        (tests/test_gpu_addressing.py checks family() of
+//                        tests/dispatch_model.py against it)
 //
 // The table's expectations are written out by hand from the rules the
 // dispatch had as one if-chain in zrc4.hip; none is computed by plan_crypt.

@@ -7,7 +7,7 @@ g++.  Here:
      the names reached are exactly the crypt-family kernels of the built
      libzrc4.so: none unreachable, none missing;
   c. for in-place range and grouped shapes the plan's family is what
-     kernel_class() of tests/test_gpu_fused_matrix.py says.
+     kernel_class() of tests/dispatch_model.py says.
 $ZSX_TOOLS_BIN (scripts/sanitize.sh) points the test at the ASan + UBSan build
 of the binary.
 """
@@ -18,7 +18,7 @@ from pathlib import Path
 
 import pytest
 
-from test_gpu_fused_matrix import kernel_class
+from dispatch_model import kernel_class
 
 ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT / "tools"))

@@ -170,12 +170,13 @@ def test_bad_declared_group_is_invalid_arg(ctx):
 
 
 def test_sweep_generator_never_overlaps_destinations():
-    """The seeded sweep of tests/test_gpu_crypt_to_rounds.py, generator only:
+    """The seeded sweep of tests/test_gpu_crypt_to_rounds.py (sweep_call of
+    tests/gpu_support.py), generator only:
     over its own ten calls and 200 more, all destination spans of all rounds
     are pairwise disjoint, sources stay inside their buffer, buckets are valid
     (one group each, no group twice, no slot twice), and the ten calls cover
     one round, several rounds, one bucket-ish and many buckets."""
-    import test_gpu_crypt_to_rounds as g
+    import gpu_support as g
     from zsummerx_amd._capi import IDLE_SLOT
     rng = np.random.default_rng(9999)                        # the sweep's seed
     seen_rounds, seen_nb = set(), set()
@@ -200,7 +201,7 @@ def test_sweep_generator_never_overlaps_destinations():
 
 
 def test_disjoint_helper_sees_an_overlap():
-    import test_gpu_crypt_to_rounds as g
+    import gpu_support as g
     off = np.array([0, 10, 30], dtype=np.uint64)
     assert g.disjoint(off, np.array([10, 20, 5], dtype=np.uint32))
     assert not g.disjoint(off, np.array([11, 20, 5], dtype=np.uint32))

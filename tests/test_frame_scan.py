@@ -13,39 +13,9 @@ import pytest
 
 import pyoracle
 from conftest import soak_seeds
+from frame_support import BOUND, frame_report, payload_report
+from gpu_support import dev
 
-BOUND = 20480
-
-
-
-def payload_report(got, want, off, ln):
-    """'' when the buffers match; else the count of differing bytes, the
-    first offsets and the sessions (entries) they fall in, with each one's
-    [off, off + len) span -- enough to tell a stray store from a wrong
-    keystream after one failing run (no reruns to reproduce)."""
-    bad = np.flatnonzero(got != want)
-    if bad.size == 0:
-        return ""
-    off = np.asarray(off, dtype=np.int64)
-    ln = np.asarray(ln, dtype=np.int64)
-    order = np.argsort(off, kind="stable")
-    ent = order[np.clip(np.searchsorted(off[order], bad[:16], side="right") - 1, 0, len(off) - 1)]
-    inside = (bad[:16] >= off[ent]) & (bad[:16] < off[ent] + ln[ent])
-    sess = sorted(set(int(e) for e in ent))
-    return (f"{bad.size} bytes differ; first offsets {bad[:16].tolist()}; entries {ent.tolist()} "
-            f"(inside their span: {inside.tolist()}); {len(np.unique(ent))} distinct among the first 16; "
-            f"spans {[(int(off[e]), int(off[e] + ln[e])) for e in sess[:4]]}; "
-            f"got {got[bad[:8]].tolist()} want {want[bad[:8]].tolist()}")
-
-
-def frame_report(w, g, name):
-    """'' when a framing output matches; else where it differs."""
-    w, g = np.asarray(w), np.asarray(g)
-    if np.array_equal(w, g):
-        return ""
-    rows = np.flatnonzero((w != g).reshape(len(w), -1).any(axis=1))
-    return (f"{name}: {rows.size} entries differ, first {rows[:8].tolist()}: "
-            f"want {w[rows[:4]].tolist()} got {g[rows[:4]].tolist()}")
 
 def pack_cases(frame_golden):
     cases = frame_golden["cases"]
@@ -125,7 +95,7 @@ def test_oracle_scan_matches_real_reference_random():
 
 # ------------------------------------------------------------------ GPU
 def device_scan(torch, c, buf, off, ln, bound, maxp):
-    T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to("cuda")
+    T = dev(torch)
     n = ln.size
     npk, used, status = (torch.zeros(n, dtype=torch.int32, device="cuda") for _ in range(3))
     pk = torch.zeros(max(1, n * maxp), dtype=torch.int32, device="cuda")
@@ -180,7 +150,7 @@ def test_decrypt_then_scan_pipeline(built):
         a, z = int(off[i]), int(off[i]) + int(ln[i])
         ct[a:z] = np.frombuffer(pyoracle.Rc4(keys[i]).encryption(ct[a:z].tobytes()), np.uint8)
     want = pyoracle.frame_scan(buf, off, ln, BOUND, 8)
-    T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to("cuda")
+    T = dev(torch)
     with Context(0, n) as c:
         c.ksa_host(keys)
         d = T(ct)
@@ -262,7 +232,7 @@ def _run_fused(n, avg, mode, seed, tail_frac=0.5):
     maxp = 8
     buf, inp, off, ln, toff, tlen, keys = _fused_case(n, avg, seed=seed, tail_frac=tail_frac)
     want = pyoracle.frame_scan(buf, off, ln, BOUND, maxp)
-    T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to("cuda")
+    T = dev(torch)
     npk, used, status = (torch.zeros(n, dtype=torch.int32, device="cuda") for _ in range(3))
     pk = torch.zeros(n * maxp, dtype=torch.int32, device="cuda")
     d = T(inp)

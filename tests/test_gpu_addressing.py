@@ -42,8 +42,9 @@ import pytest
 import pyoracle
 from addr_layout import (ARENA_BYTES, G4, M, MODES, SPLITS, WIN, base_of, check_offsets, check_spans, lines, offsets,
                          span_bytes, span_layout, window_index)
-from test_frame_scan import BOUND, frame_report
-from test_gpu_fused_matrix import kernel_class
+from dispatch_model import family
+from frame_support import BOUND, frame_report
+from gpu_support import cu_count, dev
 
 ROOT = Path(__file__).resolve().parents[1]
 IDLE = 0xFFFFFFFF                       # ZRC4_IDLE_SLOT
@@ -108,25 +109,6 @@ FORMS = {
 FORM_NAMES = list(FORMS)
 ALL_SHAPES = SHAPES + FRAME_SHAPES[-2:] + ROUNDS_SHAPES
 SHAPE_NO = {s.id: i for i, s in enumerate(ALL_SHAPES)}
-
-
-def family(call, first_slot, n, cus, io=0):
-    """The family plan_crypt (zrc4_plan.hpp) picks, stated over kernel_class
-    (tests/test_gpu_fused_matrix.py): scattered ids run the whole-group kernel
-    up to one group per CU; a rounds call never runs the window kernel;
-    declared buckets past the window kernel's 32 run crypt_decl_kernel up to
-    one bucket per CU and 256 buckets.  test_family_matches_plan_crypt holds
-    this against plan_crypt itself."""
-    G = -(-n // 256)
-    if call == "ids":
-        return "whole" if G <= cus else "stream"
-    aligned = call != "range" or first_slot % 256 == 0
-    fam = kernel_class("range" if call == "range" else "grouped", first_slot, G, cus)
-    if fam == "win" and io == 3:
-        fam = "stream" if G > cus else "half" if 2 * G <= cus and aligned else "whole"
-    if call == "declared" and fam in ("half", "whole") and G <= 256:
-        fam = "decl"
-    return fam
 
 
 LONG_SPLITS = (448, 777)                # with a 1500-byte straddler (below)
@@ -310,8 +292,8 @@ def _plan_lines(shapes):
 
 
 def test_family_matches_plan_crypt(built):
-    """family() against plan_crypt (tools/bin/plan_check plan) for every
-    (form, shape) of this module at 104, 256 and 304 CUs; at 256 CUs, an
+    """family() of tests/dispatch_model.py against plan_crypt (tools/bin/plan_check
+    plan) for every (form, shape) of this module at 104, 256 and 304 CUs; at 256 CUs, an
     MI355X's, every shape reaches the family its id names, the persistent
     write-only and out-of-place shapes take the two-launch path
     (span_fill_kernel / span_copy_kernel) and the persistent rounds shapes the
@@ -421,7 +403,8 @@ class Rig:
     def __init__(self, torch):
         from zsummerx_amd import Context
         self.torch = torch
-        self.cus = torch.cuda.get_device_properties(0).multi_processor_count
+        self.cus = cu_count(torch)
+        self.T = dev(torch)
         self.arena = torch.empty(ARENA_BYTES, dtype=torch.uint8, device="cuda")     # never touched as a whole
         self.start = self.arena.data_ptr()
         self.a1, self.a, self.a3 = lines(self.start)
@@ -436,9 +419,6 @@ class Rig:
         self.c.close()
         del self.arena
         self.torch.cuda.empty_cache()
-
-    def T(self, a):
-        return self.torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
     def reseed(self):
         rng = np.random.default_rng(5)

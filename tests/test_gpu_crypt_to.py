@@ -21,61 +21,13 @@ buckets the same four, declared and undeclared.  "Congruent" layouts keep
 import numpy as np
 import pytest
 
-import pyoracle
-from zsummerx_amd import Context, ZRC4Error
+from gpu_support import (FILL, LONG, SHORT, assert_equal, buckets, check_continues, check_states, host, layout, oracle,
+                         seeded, sources, span_index)
+from gpu_support import torch_cuda  # noqa: F401
+from zsummerx_amd import ZRC4Error
 from zsummerx_amd._capi import IDLE_SLOT
 
 pytestmark = pytest.mark.gpu
-
-FILL = 0xA5
-# the 16-byte units and the 2 KiB ring chunk of the window kernel
-LONG = np.array([0, 1, 15, 16, 17, 63, 64, 65, 2047, 2048, 2049, 4100], dtype=np.uint32)
-# head, blocks 0-3 of the A/B ping-pong, 16-byte pieces and the tail of the lane-per-stream kernels
-SHORT = np.array([0, 1, 15, 16, 17, 63, 64, 65, 127, 128, 129, 191, 192, 193, 250], dtype=np.uint32)
-TAIL = 24          # bytes per slot of the following crypt_range
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a GPU"
-    return torch
-
-
-def _oracle(seed, cap):
-    rng = np.random.default_rng(seed)
-    keys = rng.integers(0, 256, 16 * cap, dtype=np.uint8)
-    koff = np.arange(cap, dtype=np.uint64) * 16
-    klen = np.full(cap, 16, dtype=np.uint32)
-    ob = pyoracle.Batch(cap)
-    ob.make_sbox(keys, koff, klen)
-    return ob, keys, koff, klen
-
-
-def _seeded(torch, seed, cap):
-    ob, keys, koff, klen = _oracle(seed, cap)
-    T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
-    c = Context(0, cap)
-    c.ksa_range(0, T(klen.view(np.int32)), T(koff.view(np.int64)), T(keys), stream=torch.cuda.current_stream())
-    return c, ob, T
-
-
-def _layout(L, shift, cycle=3):
-    """Spans in entry order, 1..cycle guard bytes (cycling) between them, the
-    first at `shift`.  With cycle = 3 the gaps and either length list sum to an
-    odd number of bytes modulo 16 per cycle, so the start misalignment of every
-    list position walks through all of 0..15."""
-    gap = 1 + (np.arange(L.size, dtype=np.uint64) % cycle)
-    end = np.cumsum(L.astype(np.uint64) + gap)
-    off = np.concatenate(([0], end[:-1])).astype(np.uint64) + np.uint64(shift)
-    return off, int(end[-1]) + shift + 16
-
-
-def _span_index(off, L):
-    """Indexes of every span byte."""
-    L = L.astype(np.int64)
-    start = np.cumsum(L) - L
-    return np.repeat(off.astype(np.int64) - start, L) + np.arange(int(L.sum()), dtype=np.int64)
 
 
 def _want(ob, cap, size, slots, src, soff, doff, L, base=None):
@@ -83,47 +35,13 @@ def _want(ob, cap, size, slots, src, soff, doff, L, base=None):
     source bytes of entry i gathered into span i and crypted there by the
     oracle as slot slots[i]; the oracle advanced."""
     want = np.full(size, FILL, dtype=np.uint8) if base is None else base.copy()
-    want[_span_index(doff, L)] = src[_span_index(soff, L)]
+    want[span_index(doff, L)] = src[span_index(soff, L)]
     so = np.zeros(cap, dtype=np.uint64)
     sl = np.zeros(cap, dtype=np.uint32)
     so[slots] = doff
     sl[slots] = L
     ob.crypt(want, so, sl)
     return want
-
-
-def _check_states(c, ob, cap):
-    gsb, gx, gy = c.get_states(0, cap)
-    osb, ox, oy = ob.states()
-    bad = np.flatnonzero((gsb != osb).any(axis=1) | (gx != ox) | (gy != oy))
-    assert bad.size == 0, bad[:8]
-
-
-def _check_continues(torch, c, ob, T, cap, rng):
-    """Every state; then crypt_range of TAIL random bytes per slot of the whole
-    context goes on where the oracle's streams are; then every state again."""
-    _check_states(c, ob, cap)
-    s = torch.cuda.current_stream()
-    data = rng.integers(0, 256, cap * TAIL, dtype=np.uint8)
-    off = np.arange(cap, dtype=np.uint64) * TAIL
-    L = np.full(cap, TAIL, dtype=np.uint32)
-    want = data.copy()
-    ob.crypt(want, off, L)
-    pay = T(data)
-    c.crypt_range(0, pay, T(off.view(np.int64)), T(L.view(np.int32)), stream=s)
-    c.sync(s)
-    bad = np.flatnonzero(pay.cpu().numpy() != want)
-    assert bad.size == 0, ("following crypt_range", bad[:8] // TAIL, int(bad.size))
-    _check_states(c, ob, cap)
-
-
-def _assert_equal(got, want, what):
-    bad = np.flatnonzero(got != want)
-    assert bad.size == 0, (what, bad[:8], int(bad.size), got[bad[:8]], want[bad[:8]])
-
-
-def _host(t):
-    return t.cpu().numpy() if t.is_cuda else t.numpy()
 
 
 def _run_range(torch, c, ob, T, cap, first, src, soff, doff, L, size, what, Tsrc=None, Tdst=None):
@@ -135,8 +53,8 @@ def _run_range(torch, c, ob, T, cap, first, src, soff, doff, L, size, what, Tsrc
     td = (Tdst or T)(np.full(size, FILL, dtype=np.uint8))
     c.crypt_to_range(first, ts, T(soff.view(np.int64)), td, T(doff.view(np.int64)), T(L.view(np.int32)), stream=s)
     c.sync(s)
-    _assert_equal(_host(td), want, what)
-    _assert_equal(_host(ts), src, what + ": source changed")
+    assert_equal(host(td), want, what)
+    assert_equal(host(ts), src, what + ": source changed")
 
 
 # -- range ---------------------------------------------------------------------
@@ -149,24 +67,24 @@ def test_crypt_to_range_whole_groups(built, torch_cuda, groups, congruent):
     lens = LONG if groups <= 32 else SHORT
     n = 256 * groups
     cap = n + 256                                        # one group the call does not touch
-    c, ob, T = _seeded(torch, 8100 + groups, cap)
+    c, ob, T = seeded(torch, 8100 + groups, cap)
     with c:
         pos = np.arange(n) % lens.size
         L = lens[pos]
-        doff, size = _layout(L, groups % 16)
+        doff, size = layout(L, groups % 16)
         # every length of the list meets every start misalignment of the destination
         pairs = set(zip(pos.tolist(), (doff % 16).tolist()))
         assert len(pairs) == 16 * lens.size or n < 16 * lens.size, len(pairs)
         if congruent:
             soff, ssize = doff + np.uint64(48), size + 48
         else:
-            soff, ssize = _layout(L, (groups + 5) % 16, cycle=5)
+            soff, ssize = layout(L, (groups + 5) % 16, cycle=5)
             d = ((soff.astype(np.int64) - doff.astype(np.int64)) % 16)
             for k in range(lens.size):                   # nonzero (src - dst) mod 16 for every length of the list
                 assert (d[pos == k] != 0).any(), k
         src = rng.integers(0, 256, ssize, dtype=np.uint8)
         _run_range(torch, c, ob, T, cap, 0, src, soff, doff, L, size, "crypt_to_range")
-        _check_continues(torch, c, ob, T, cap, rng)
+        check_continues(torch, c, ob, T, cap, rng)
 
 
 def test_crypt_to_range_unaligned_first_slot(built, torch_cuda):
@@ -175,16 +93,16 @@ def test_crypt_to_range_unaligned_first_slot(built, torch_cuda):
     torch = torch_cuda
     rng = np.random.default_rng(7400)
     first, n, cap = 3, 700, 1024
-    c, ob, T = _seeded(torch, 8400, cap)
+    c, ob, T = seeded(torch, 8400, cap)
     with c:
         L = SHORT[np.arange(n) % SHORT.size]
-        doff, size = _layout(L, 7)
-        soff, ssize = _layout(L, 2, cycle=5)
+        doff, size = layout(L, 7)
+        soff, ssize = layout(L, 2, cycle=5)
         soff[::2] = doff[::2] + np.uint64(32)            # every other entry congruent
         ssize = max(ssize, size + 32)
         src = rng.integers(0, 256, ssize, dtype=np.uint8)
         _run_range(torch, c, ob, T, cap, first, src, soff, doff, L, size, "crypt_to_range first_slot=3")
-        _check_continues(torch, c, ob, T, cap, rng)
+        check_continues(torch, c, ob, T, cap, rng)
 
 
 # -- broadcast -------------------------------------------------------------------
@@ -201,18 +119,18 @@ def test_crypt_to_broadcast(built, torch_cuda, groups, length):
     rng = np.random.default_rng(7500 + groups + max(length, 0))
     n = 256 * groups
     cap = n + 256
-    c, ob, T = _seeded(torch, 8500 + groups, cap)
+    c, ob, T = seeded(torch, 8500 + groups, cap)
     with c:
         if length > 0:
             L = np.full(n, length, dtype=np.uint32)
         else:
             lens = LONG if length == -1 else SHORT
             L = lens[np.arange(n) % lens.size]
-        doff, size = _layout(L, 3)
+        doff, size = layout(L, 3)
         soff = np.full(n, 21, dtype=np.uint64)
         src = rng.integers(0, 256, 21 + int(L.max()) + 9, dtype=np.uint8)
         _run_range(torch, c, ob, T, cap, 0, src, soff, doff, L, size, "broadcast")
-        _check_continues(torch, c, ob, T, cap, rng)
+        check_continues(torch, c, ob, T, cap, rng)
 
 
 # -- in place through the new call --------------------------------------------------
@@ -225,40 +143,28 @@ def test_crypt_to_in_place(built, torch_cuda, groups):
     lens = LONG if groups <= 32 else SHORT
     n = 256 * groups
     cap = n + 256
-    c, ob, T = _seeded(torch, 8600 + groups, cap)
+    c, ob, T = seeded(torch, 8600 + groups, cap)
     s = torch.cuda.current_stream()
     with c:
         L = lens[np.arange(n) % lens.size]
-        off, size = _layout(L, groups % 16)
+        off, size = layout(L, groups % 16)
         data = rng.integers(0, 256, size, dtype=np.uint8)
         want = data.copy()
         ob.crypt(want, np.concatenate((off, np.zeros(256, np.uint64))), np.concatenate((L, np.zeros(256, np.uint32))))
         buf, toff = T(data), T(off.view(np.int64))
         c.crypt_to_range(0, buf, toff, buf, toff, T(L.view(np.int32)), stream=s)
         c.sync(s)
-        _assert_equal(buf.cpu().numpy(), want, "in place through crypt_to_range")
-        _check_continues(torch, c, ob, T, cap, rng)
+        assert_equal(buf.cpu().numpy(), want, "in place through crypt_to_range")
+        check_continues(torch, c, ob, T, cap, rng)
 
 
 # -- grouped -------------------------------------------------------------------
-
-def _buckets(rng, groups):
-    """Bucket b: a random subset (1-256 slots) of group groups[b] in shuffled
-    entry positions, IDLE_SLOT elsewhere; groups[b] == IDLE_SLOT: an idle bucket."""
-    ids = np.full(256 * len(groups), IDLE_SLOT, dtype=np.uint32)
-    for b, g in enumerate(groups):
-        if g == IDLE_SLOT:
-            continue
-        k = int(rng.integers(1, 257))
-        ids[256 * b + rng.permutation(256)[:k]] = int(g) * 256 + rng.permutation(256)[:k]
-    return ids
-
 
 def _grouped_case(rng, nb, G, idle_bucket=True):
     groups = rng.permutation(G)[:nb].astype(np.uint32)
     if idle_bucket:
         groups[nb // 2] = IDLE_SLOT
-    ids = _buckets(rng, groups)
+    ids = buckets(rng, groups)
     # every entry has a span (idle entries too: theirs must stay 0xA5);
     # SHORT holds a zero, so some busy entries have len == 0
     L = SHORT[rng.integers(0, SHORT.size, ids.size)]
@@ -268,20 +174,6 @@ def _grouped_case(rng, nb, G, idle_bucket=True):
     assert busy.size and idle.size
     L[idle[idle.size // 2]] = 17                         # and an idle one with a span to keep
     return groups, ids, L
-
-
-def _sources(rng, L, doff):
-    """Sources of a grouped case: a third of the entries share one message (a
-    prefix of it each), a third are congruent with their destination, the rest
-    lie wherever the source layout puts them."""
-    soff, ssize = _layout(L, 11, cycle=5)
-    kind = rng.integers(0, 3, L.size)
-    cong = kind == 1
-    soff[cong] += (doff[cong] - soff[cong]) % np.uint64(16)        # (may run into the next source: allowed)
-    shared = ssize + 5
-    soff[kind == 0] = shared
-    ssize = shared + int(L.max()) + 16
-    return soff, ssize
 
 
 def _run_grouped(torch, c, ob, T, cap, ids, groups, src, soff, doff, L, size, ran, what):
@@ -300,12 +192,12 @@ def test_crypt_to_grouped(built, torch_cuda, nb, declared):
     rng = np.random.default_rng(7700 + nb + declared)
     G = nb + 8
     cap = 256 * G
-    c, ob, T = _seeded(torch, 8700 + nb, cap)
+    c, ob, T = seeded(torch, 8700 + nb, cap)
     s = torch.cuda.current_stream()
     with c:
         groups, ids, L = _grouped_case(rng, nb, G)
-        doff, size = _layout(L, nb % 16)
-        soff, ssize = _sources(rng, L, doff)
+        doff, size = layout(L, nb % 16)
+        soff, ssize = sources(rng, L, doff)
         busy = ids != IDLE_SLOT
         assert (L[busy] == 0).any() and (L[~busy] != 0).any()
         d = (soff.astype(np.int64) - doff.astype(np.int64)) % 16
@@ -314,9 +206,9 @@ def test_crypt_to_grouped(built, torch_cuda, nb, declared):
         want, ts, td = _run_grouped(torch, c, ob, T, cap, ids, groups if declared else None, src, soff, doff, L, size,
                                     busy, "grouped")
         c.sync(s)
-        _assert_equal(td.cpu().numpy(), want, "crypt_to_grouped")
-        _assert_equal(ts.cpu().numpy(), src, "crypt_to_grouped: source changed")
-        _check_continues(torch, c, ob, T, cap, rng)
+        assert_equal(td.cpu().numpy(), want, "crypt_to_grouped")
+        assert_equal(ts.cpu().numpy(), src, "crypt_to_grouped: source changed")
+        check_continues(torch, c, ob, T, cap, rng)
 
 
 def test_crypt_to_grouped_id_out_of_range(built, torch_cuda):
@@ -327,15 +219,15 @@ def test_crypt_to_grouped_id_out_of_range(built, torch_cuda):
     rng = np.random.default_rng(7900)
     G = nb + 8
     cap = 256 * G
-    c, ob, T = _seeded(torch, 8900, cap)
+    c, ob, T = seeded(torch, 8900, cap)
     s = torch.cuda.current_stream()
     with c:
         groups, ids, L = _grouped_case(rng, nb, G, idle_bucket=False)
         e = int(np.flatnonzero(ids[:256] == IDLE_SLOT)[0]) if (ids[:256] == IDLE_SLOT).any() else 0
         ids[e] = cap + 77
         L[e] = 193
-        doff, size = _layout(L, nb % 16)
-        soff, ssize = _sources(rng, L, doff)
+        doff, size = layout(L, nb % 16)
+        soff, ssize = sources(rng, L, doff)
         ran = (ids != IDLE_SLOT) & (ids < cap)
         src = rng.integers(0, 256, ssize, dtype=np.uint8)
         want, ts, td = _run_grouped(torch, c, ob, T, cap, ids, groups, src, soff, doff, L, size, ran, "range fault")
@@ -344,9 +236,9 @@ def test_crypt_to_grouped_id_out_of_range(built, torch_cuda):
         assert ei.value.code == -5                         # ZRC4_ERR_SLOT_RANGE
         got = td.cpu().numpy()
         assert (got[int(doff[e]): int(doff[e]) + 193] == FILL).all()
-        _assert_equal(got, want, "id out of range")
-        _assert_equal(ts.cpu().numpy(), src, "id out of range: source changed")
-        _check_continues(torch, c, ob, T, cap, rng)
+        assert_equal(got, want, "id out of range")
+        assert_equal(ts.cpu().numpy(), src, "id out of range: source changed")
+        check_continues(torch, c, ob, T, cap, rng)
 
 
 # -- refusal -------------------------------------------------------------------
@@ -366,7 +258,7 @@ def test_crypt_to_grouped_two_buckets_one_group(built, torch_cuda, nb, declared)
     G = nb + 8
     cap = 256 * G
     seed = 8800 + nb
-    c, ob, T = _seeded(torch, seed, cap)
+    c, ob, T = seeded(torch, seed, cap)
     s = torch.cuda.current_stream()
     with c:
         groups, ids, L = _grouped_case(rng, nb, G, idle_bucket=False)
@@ -377,12 +269,12 @@ def test_crypt_to_grouped_two_buckets_one_group(built, torch_cuda, nb, declared)
         ids[rng.permutation(256)[:100]] = g * 256 + perm[:100]
         ids[256 + rng.permutation(256)[:100]] = g * 256 + perm[100:200]
         L[:512] = np.maximum(L[:512], 16)                # long enough to tell crypted from copied or untouched
-        doff, size = _layout(L, nb % 16)
-        soff, ssize = _sources(rng, L, doff)
+        doff, size = layout(L, nb % 16)
+        soff, ssize = sources(rng, L, doff)
         src = rng.integers(0, 256, ssize, dtype=np.uint8)
         busy = ids != IDLE_SLOT
         # what every span would hold had every entry run (a second oracle)
-        all_ran = _want(_oracle(seed, cap)[0], cap, size, ids[busy], src, soff[busy], doff[busy], L[busy])
+        all_ran = _want(oracle(seed, cap)[0], cap, size, ids[busy], src, soff[busy], doff[busy], L[busy])
         ts, td = T(src.copy()), T(np.full(size, FILL, dtype=np.uint8))
         c.crypt_to_grouped(ts, T(soff.view(np.int64)), td, T(doff.view(np.int64)), T(L.view(np.int32)),
                            T(ids.view(np.int32)), groups if declared else None, stream=s)
@@ -402,9 +294,9 @@ def test_crypt_to_grouped_two_buckets_one_group(built, torch_cuda, nb, declared)
             sp[:] = FILL
         assert not ran[:512][busy[:512]].all()           # somebody was refused
         want = _want(ob, cap, size, ids[ran], src, soff[ran], doff[ran], L[ran])
-        _assert_equal(got, want, "two buckets, one group")
-        _assert_equal(ts.cpu().numpy(), src, "refusal: source changed")
-        _check_continues(torch, c, ob, T, cap, rng)        # (states: the oracle ran exactly the slots that ran)
+        assert_equal(got, want, "two buckets, one group")
+        assert_equal(ts.cpu().numpy(), src, "refusal: source changed")
+        check_continues(torch, c, ob, T, cap, rng)        # (states: the oracle ran exactly the slots that ran)
 
 
 # -- pinned host memory ----------------------------------------------------------------
@@ -417,18 +309,18 @@ def test_crypt_to_pinned_host(built, torch_cuda, groups, where):
     lens = LONG if groups <= 32 else SHORT
     n = 256 * groups
     cap = n + 256
-    c, ob, T = _seeded(torch, 8950 + groups, cap)
+    c, ob, T = seeded(torch, 8950 + groups, cap)
     P = lambda a: torch.from_numpy(np.ascontiguousarray(a)).pin_memory()
     with c:
         L = lens[np.arange(n) % lens.size]
-        doff, size = _layout(L, 9)
-        soff, ssize = _layout(L, 4, cycle=5)
+        doff, size = layout(L, 9)
+        soff, ssize = layout(L, 4, cycle=5)
         soff[::2] = doff[::2] + np.uint64(16)
         ssize = max(ssize, size + 16)
         src = rng.integers(0, 256, ssize, dtype=np.uint8)
         _run_range(torch, c, ob, T, cap, 0, src, soff, doff, L, size, where,
                    Tsrc=P if where == "src_pinned" else None, Tdst=P if where == "dst_pinned" else None)
-        _check_continues(torch, c, ob, T, cap, rng)
+        check_continues(torch, c, ob, T, cap, rng)
 
 
 # -- random sweep ----------------------------------------------------------------------
@@ -442,7 +334,7 @@ def test_crypt_to_random_sweep(built, torch_cuda):
     rng = np.random.default_rng(7999)
     counts = [1, 2, 3, 31, 32, 33, 34, 127, 128, 129, 130, 255, 256, 257, 258]
     cap = 259 * 256
-    c, ob, T = _seeded(torch, 8999, cap)
+    c, ob, T = seeded(torch, 8999, cap)
     with c:
         for call in range(20):
             groups = int(counts[call] if call < len(counts) else rng.choice(counts))
@@ -461,5 +353,5 @@ def test_crypt_to_random_sweep(built, torch_cuda):
             ok = adj + L[some].astype(np.uint64) <= ssize
             soff[np.flatnonzero(some)[ok]] = adj[ok]
             _run_range(torch, c, ob, T, cap, 0, src, soff, doff, L, size, f"sweep call {call} ({groups} groups)")
-            _check_states(c, ob, cap)
-        _check_continues(torch, c, ob, T, cap, rng)
+            check_states(c, ob, cap)
+        check_continues(torch, c, ob, T, cap, rng)

@@ -22,68 +22,19 @@ kernels, declared and undeclared."""
 import numpy as np
 import pytest
 
-import pyoracle
-from zsummerx_amd import Context, ZRC4Error
+from dispatch_model import rounds_groups
+from gpu_support import (FILL, SWEEP_CALLS, SWEEP_GROUPS, assert_equal, buckets, check_continues, check_states, cu_count,
+                         disjoint, host, layout, oracle, seeded, span_index, sweep_call)
+from gpu_support import torch_cuda  # noqa: F401
+from zsummerx_amd import ZRC4Error
 from zsummerx_amd._capi import IDLE_SLOT
 
 gpu = pytest.mark.gpu
 
-FILL = 0xA5
-TAIL = 24          # bytes per slot of the following crypt_range
 # nothing, head or tail bytes only, one 16-byte piece and around it, one block
 # and around it, four blocks with pieces and a tail
 LENS = np.array([0, 1, 15, 16, 17, 63, 64, 65, 300], dtype=np.uint32)
 HEAD_ONLY = np.array([1, 15], dtype=np.uint32)         # (300 bytes run the block loop at any alignment)
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a GPU"
-    return torch
-
-
-def _oracle(seed, cap):
-    rng = np.random.default_rng(seed)
-    keys = rng.integers(0, 256, 16 * cap, dtype=np.uint8)
-    koff = np.arange(cap, dtype=np.uint64) * 16
-    klen = np.full(cap, 16, dtype=np.uint32)
-    ob = pyoracle.Batch(cap)
-    ob.make_sbox(keys, koff, klen)
-    return ob, keys, koff, klen
-
-
-def _seeded(torch, seed, cap):
-    ob, keys, koff, klen = _oracle(seed, cap)
-    T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
-    c = Context(0, cap)
-    c.ksa_range(0, T(klen.view(np.int32)), T(koff.view(np.int64)), T(keys), stream=torch.cuda.current_stream())
-    return c, ob, T
-
-
-def _layout(L, shift, cycle=3):
-    """Spans in list order, 1..cycle guard bytes (cycling) between them, the
-    first at `shift`: offsets and the buffer size."""
-    gap = 1 + (np.arange(L.size, dtype=np.uint64) % cycle)
-    end = np.cumsum(L.astype(np.uint64) + gap)
-    off = np.concatenate(([0], end[:-1])).astype(np.uint64) + np.uint64(shift)
-    return off, int(end[-1]) + shift + 16
-
-
-def _span_index(off, L):
-    """Indexes of every span byte."""
-    L = L.astype(np.int64)
-    start = np.cumsum(L) - L
-    return np.repeat(off.astype(np.int64) - start, L) + np.arange(int(L.sum()), dtype=np.int64)
-
-
-def disjoint(off, L):
-    """No two of the spans [off, off + L) with L > 0 share a byte."""
-    keep = L > 0
-    o, l = off[keep].astype(np.int64), L[keep].astype(np.int64)
-    order = np.argsort(o, kind="stable")
-    o, l = o[order], l[order]
-    return bool((o[1:] >= o[:-1] + l[:-1]).all())
 
 
 def _want(ob, cap, base, slots, ran, src, soff, doff, L, rounds):
@@ -94,47 +45,13 @@ def _want(ob, cap, base, slots, ran, src, soff, doff, L, rounds):
     n = slots.size
     for r in range(rounds):
         so, do, l = soff[r * n:(r + 1) * n][ran], doff[r * n:(r + 1) * n][ran], L[r * n:(r + 1) * n][ran]
-        want[_span_index(do, l)] = src[_span_index(so, l)]
+        want[span_index(do, l)] = src[span_index(so, l)]
         po = np.zeros(cap, dtype=np.uint64)
         pl = np.zeros(cap, dtype=np.uint32)
         po[slots[ran]] = do
         pl[slots[ran]] = l
         ob.crypt(want, po, pl)
     return want
-
-
-def _check_states(c, ob, cap):
-    gsb, gx, gy = c.get_states(0, cap)
-    osb, ox, oy = ob.states()
-    bad = np.flatnonzero((gsb != osb).any(axis=1) | (gx != ox) | (gy != oy))
-    assert bad.size == 0, bad[:8]
-
-
-def _check_continues(torch, c, ob, T, cap, rng):
-    """Every state; then crypt_range of TAIL random bytes per slot of the whole
-    context goes on where the oracle's streams are; then every state again."""
-    _check_states(c, ob, cap)
-    s = torch.cuda.current_stream()
-    data = rng.integers(0, 256, cap * TAIL, dtype=np.uint8)
-    off = np.arange(cap, dtype=np.uint64) * TAIL
-    L = np.full(cap, TAIL, dtype=np.uint32)
-    want = data.copy()
-    ob.crypt(want, off, L)
-    pay = T(data)
-    c.crypt_range(0, pay, T(off.view(np.int64)), T(L.view(np.int32)), stream=s)
-    c.sync(s)
-    bad = np.flatnonzero(pay.cpu().numpy() != want)
-    assert bad.size == 0, ("following crypt_range", bad[:8] // TAIL, int(bad.size))
-    _check_states(c, ob, cap)
-
-
-def _assert_equal(got, want, what):
-    bad = np.flatnonzero(got != want)
-    assert bad.size == 0, (what, bad[:8], int(bad.size), got[bad[:8]], want[bad[:8]])
-
-
-def _host(t):
-    return t.cpu().numpy() if t.is_cuda else t.numpy()
 
 
 def _round_lengths(rng, n, rounds):
@@ -161,7 +78,7 @@ def _range_tables(rng, n, rounds, congruent, shift):
     own place in the destination; sources 48 bytes on in a buffer of their own
     (congruent), or 49..63 bytes on ((src - dst) mod 16 nonzero everywhere)."""
     L = _round_lengths(rng, n, rounds).reshape(-1)
-    doff, size = _layout(L, shift)
+    doff, size = layout(L, shift)
     if congruent:
         soff = doff + np.uint64(48)
     else:
@@ -181,16 +98,11 @@ def _run_range(torch, c, ob, T, cap, first, n, rounds, src, soff, doff, L, size,
     c.crypt_to_range_rounds(first, ts, T(soff.view(np.int64)), td, T(doff.view(np.int64)), T(L.view(np.int32)), n,
                             rounds, stream=s)
     c.sync(s)
-    _assert_equal(_host(td), want, what)
-    _assert_equal(_host(ts), src, what + ": source changed")
+    assert_equal(host(td), want, what)
+    assert_equal(host(ts), src, what + ": source changed")
 
 
 # -- range ---------------------------------------------------------------------
-
-def _groups(torch, which):
-    cus = torch.cuda.get_device_properties(0).multi_processor_count
-    return {"1": 1, "33": 33, "half+1": cus // 2 + 1, "257": 257}[which]
-
 
 @gpu
 @pytest.mark.parametrize("congruent", [True, False], ids=["congruent", "noncongruent"])
@@ -198,16 +110,16 @@ def _groups(torch, which):
                                           ("half+1", 5), ("257", 2), ("257", 5)])
 def test_rounds_range_whole_groups(built, torch_cuda, which, rounds, congruent):
     torch = torch_cuda
-    groups = _groups(torch, which)
+    groups = rounds_groups(which, cu_count(torch))
     rng = np.random.default_rng(9100 + 100 * groups + rounds)
     n = 256 * groups
     cap = n + 256                                        # one group the call does not touch
-    c, ob, T = _seeded(torch, 9200 + groups, cap)
+    c, ob, T = seeded(torch, 9200 + groups, cap)
     with c:
         L, doff, size, soff, ssize = _range_tables(rng, n, rounds, congruent, groups % 16)
         src = rng.integers(0, 256, ssize, dtype=np.uint8)
         _run_range(torch, c, ob, T, cap, 0, n, rounds, src, soff, doff, L, size, f"{groups} groups x {rounds} rounds")
-        _check_continues(torch, c, ob, T, cap, rng)
+        check_continues(torch, c, ob, T, cap, rng)
 
 
 @gpu
@@ -218,13 +130,13 @@ def test_rounds_range_unaligned_first_slot(built, torch_cuda, rounds):
     torch = torch_cuda
     rng = np.random.default_rng(9300 + rounds)
     first, n, cap = 3, 700, 1024
-    c, ob, T = _seeded(torch, 9301, cap)
+    c, ob, T = seeded(torch, 9301, cap)
     with c:
         L, doff, size, soff, ssize = _range_tables(rng, n, rounds, False, 7)
         soff[::2] = doff[::2] + np.uint64(32)
         src = rng.integers(0, 256, ssize, dtype=np.uint8)
         _run_range(torch, c, ob, T, cap, first, n, rounds, src, soff, doff, L, size, "first_slot=3")
-        _check_continues(torch, c, ob, T, cap, rng)
+        check_continues(torch, c, ob, T, cap, rng)
 
 
 # -- equivalence ---------------------------------------------------------------
@@ -236,13 +148,13 @@ def test_rounds_equal_successive_calls(built, torch_cuda, which):
     calls on context B with the same seeds: the same destination bytes and the
     same states (at 1 group B runs the window kernel, A the half-group one)."""
     torch = torch_cuda
-    groups, rounds = _groups(torch, which), 4
+    groups, rounds = rounds_groups(which, cu_count(torch)), 4
     rng = np.random.default_rng(9400 + groups)
     n = 256 * groups
     cap = n + 256
     s = torch.cuda.current_stream()
-    a, _, T = _seeded(torch, 9401, cap)
-    b, _, _ = _seeded(torch, 9401, cap)
+    a, _, T = seeded(torch, 9401, cap)
+    b, _, _ = seeded(torch, 9401, cap)
     with a, b:
         L, doff, size, soff, ssize = _range_tables(rng, n, rounds, False, 5)
         soff[::3] = doff[::3] + np.uint64(16)
@@ -256,24 +168,12 @@ def test_rounds_equal_successive_calls(built, torch_cuda, which):
             b.crypt_to_range(0, ts, tso[w], db, tdo[w], tl[w], n, stream=s)
         a.sync(s)
         b.sync(s)
-        _assert_equal(da.cpu().numpy(), db.cpu().numpy(), "rounds call against successive calls")
+        assert_equal(da.cpu().numpy(), db.cpu().numpy(), "rounds call against successive calls")
         for x, y in zip(a.get_states(0, cap), b.get_states(0, cap)):
             assert (np.asarray(x) == np.asarray(y)).all()
 
 
 # -- grouped: queued bytes in place, then three broadcasts -----------------------------
-
-def _buckets(rng, groups):
-    """Bucket b: a random subset (1-256 slots) of group groups[b] in shuffled
-    entry positions, IDLE_SLOT elsewhere; groups[b] == IDLE_SLOT: an idle bucket."""
-    ids = np.full(256 * len(groups), IDLE_SLOT, dtype=np.uint32)
-    for b, g in enumerate(groups):
-        if g == IDLE_SLOT:
-            continue
-        k = int(rng.integers(1, 257))
-        ids[256 * b + rng.permutation(256)[:k]] = int(g) * 256 + rng.permutation(256)[:k]
-    return ids
-
 
 MSG = (100, 64, 37)        # the three broadcast messages' lengths
 
@@ -287,7 +187,7 @@ def _tick_case(rng, ids):
     n, rounds = ids.size, 4
     q = LENS[rng.integers(0, LENS.size, n)]
     run = q.astype(np.uint64) + np.uint64(sum(MSG))
-    start, end = _layout(run, 9)
+    start, end = layout(run, 9)
     L = np.zeros((rounds, n), dtype=np.uint32)
     doff = np.zeros((rounds, n), dtype=np.uint64)
     soff = np.zeros((rounds, n), dtype=np.uint64)
@@ -311,13 +211,13 @@ def test_rounds_grouped_queue_then_broadcasts(built, torch_cuda, nb, declared):
     rng = np.random.default_rng(9500 + nb + declared)
     G = nb + 8
     cap = 256 * G
-    c, ob, T = _seeded(torch, 9501 + nb, cap)
+    c, ob, T = seeded(torch, 9501 + nb, cap)
     s = torch.cuda.current_stream()
     with c:
         groups = rng.permutation(G)[:nb].astype(np.uint32)
         if nb > 2:
             groups[nb // 2] = IDLE_SLOT
-        ids = _buckets(rng, groups)
+        ids = buckets(rng, groups)
         ids[np.flatnonzero(ids != IDLE_SLOT)[::7]] = IDLE_SLOT             # idle slots inside busy buckets too
         busy = ids != IDLE_SLOT
         assert busy.any() and not busy.all()
@@ -332,10 +232,10 @@ def test_rounds_grouped_queue_then_broadcasts(built, torch_cuda, nb, declared):
                                   stream=s)
         c.sync(s)
         got = buf.cpu().numpy()
-        _assert_equal(got, want, "queue in place, then three broadcasts")
+        assert_equal(got, want, "queue in place, then three broadcasts")
         # (want outside the spans that ran is `data`: guards, idle entries' runs and the messages unchanged)
-        _assert_equal(got[msgs_at:], data[msgs_at:], "the broadcast sources changed")
-        _check_continues(torch, c, ob, T, cap, rng)
+        assert_equal(got[msgs_at:], data[msgs_at:], "the broadcast sources changed")
+        check_continues(torch, c, ob, T, cap, rng)
 
 
 # -- faults and refusals -----------------------------------------------------------
@@ -345,8 +245,8 @@ def _grouped_tables(rng, n, rounds, shift):
     the entry-rounds read one shared message (a prefix each), a third are
     congruent with their destination, the rest lie anywhere."""
     L = _round_lengths(rng, n, rounds).reshape(-1)
-    doff, size = _layout(L, shift)
-    soff, ssize = _layout(L, 11, cycle=5)
+    doff, size = layout(L, shift)
+    soff, ssize = layout(L, 11, cycle=5)
     kind = rng.integers(0, 3, L.size)
     cong = kind == 1
     soff[cong] += (doff[cong] - soff[cong]) % np.uint64(16)        # (may run into the next source: allowed)
@@ -364,17 +264,17 @@ def test_rounds_grouped_id_out_of_range(built, torch_cuda):
     rng = np.random.default_rng(9600)
     G = nb + 8
     cap = 256 * G
-    c, ob, T = _seeded(torch, 9601, cap)
+    c, ob, T = seeded(torch, 9601, cap)
     s = torch.cuda.current_stream()
     with c:
         groups = rng.permutation(G)[:nb].astype(np.uint32)
-        ids = _buckets(rng, groups)
+        ids = buckets(rng, groups)
         n = ids.size
         e = int(np.flatnonzero(ids[:256] == IDLE_SLOT)[0]) if (ids[:256] == IDLE_SLOT).any() else 0
         ids[e] = cap + 77
         L, doff, size, soff, ssize = _grouped_tables(rng, n, rounds, 4)
         L[e::n] = 193                                    # a span to keep in every round
-        doff, size = _layout(L, 4)
+        doff, size = layout(L, 4)
         assert disjoint(doff, L)
         ran = (ids != IDLE_SLOT) & (ids < cap)
         src = rng.integers(0, 256, ssize, dtype=np.uint8)
@@ -390,9 +290,9 @@ def test_rounds_grouped_id_out_of_range(built, torch_cuda):
         for r in range(rounds):
             a = int(doff[r * n + e])
             assert (got[a: a + 193] == FILL).all(), r
-        _assert_equal(got, want, "id out of range")
-        _assert_equal(ts.cpu().numpy(), src, "id out of range: source changed")
-        _check_continues(torch, c, ob, T, cap, rng)
+        assert_equal(got, want, "id out of range")
+        assert_equal(ts.cpu().numpy(), src, "id out of range: source changed")
+        check_continues(torch, c, ob, T, cap, rng)
 
 
 @gpu
@@ -409,7 +309,7 @@ def test_rounds_grouped_two_buckets_one_group(built, torch_cuda, declared):
     G = nb + 8
     cap = 256 * G
     seed = 9701
-    c, ob, T = _seeded(torch, seed, cap)
+    c, ob, T = seeded(torch, seed, cap)
     s = torch.cuda.current_stream()
     with c:
         g = 5
@@ -421,7 +321,7 @@ def test_rounds_grouped_two_buckets_one_group(built, torch_cuda, declared):
         n = ids.size
         L, doff, size, soff, ssize = _grouped_tables(rng, n, rounds, 2)
         L = np.maximum(L, 16)                            # long enough to tell crypted from untouched, in every round
-        doff, size = _layout(L, 2)
+        doff, size = layout(L, 2)
         soff, ssize = doff + np.uint64(32), size + 32
         soff[1::2] += np.uint64(5)
         assert disjoint(doff, L)
@@ -429,7 +329,7 @@ def test_rounds_grouped_two_buckets_one_group(built, torch_cuda, declared):
         busy = ids != IDLE_SLOT
         slots = np.where(busy, ids, 0)
         blank = np.full(size, FILL, dtype=np.uint8)
-        all_ran = _want(_oracle(seed, cap)[0], cap, blank, slots, busy, src, soff, doff, L, rounds)
+        all_ran = _want(oracle(seed, cap)[0], cap, blank, slots, busy, src, soff, doff, L, rounds)
         ts, td = T(src.copy()), T(blank)
         c.crypt_to_grouped_rounds(ts, T(soff.view(np.int64)), td, T(doff.view(np.int64)), T(L.view(np.int32)),
                                   T(ids.view(np.int32)), n, rounds, bucket_group=groups if declared else None,
@@ -447,9 +347,9 @@ def test_rounds_grouped_two_buckets_one_group(built, torch_cuda, declared):
             assert all((got[a:z] == FILL).all() for a, z in spans), (e, [got[a:a + 8] for a, _ in spans])
         assert not ran[busy].all()                       # somebody was refused
         want = _want(ob, cap, blank, slots, ran, src, soff, doff, L, rounds)
-        _assert_equal(got, want, "two buckets, one group")
-        _assert_equal(ts.cpu().numpy(), src, "refusal: source changed")
-        _check_continues(torch, c, ob, T, cap, rng)        # (states: the oracle ran exactly the slots that ran)
+        assert_equal(got, want, "two buckets, one group")
+        assert_equal(ts.cpu().numpy(), src, "refusal: source changed")
+        check_continues(torch, c, ob, T, cap, rng)        # (states: the oracle ran exactly the slots that ran)
 
 
 # -- pinned host memory ----------------------------------------------------------------
@@ -461,7 +361,7 @@ def test_rounds_pinned_host(built, torch_cuda, where):
     rng = np.random.default_rng(9800)
     n, rounds = 256, 3
     cap = n + 256
-    c, ob, T = _seeded(torch, 9801, cap)
+    c, ob, T = seeded(torch, 9801, cap)
     P = lambda a: torch.from_numpy(np.ascontiguousarray(a)).pin_memory()
     with c:
         L, doff, size, soff, ssize = _range_tables(rng, n, rounds, False, 9)
@@ -469,44 +369,10 @@ def test_rounds_pinned_host(built, torch_cuda, where):
         src = rng.integers(0, 256, ssize, dtype=np.uint8)
         _run_range(torch, c, ob, T, cap, 0, n, rounds, src, soff, doff, L, size, where,
                    Tsrc=P if where == "src_pinned" else None, Tdst=P if where == "dst_pinned" else None)
-        _check_continues(torch, c, ob, T, cap, rng)
+        check_continues(torch, c, ob, T, cap, rng)
 
 
 # -- seeded sweep ----------------------------------------------------------------------
-
-SWEEP_CALLS, SWEEP_GROUPS = 10, 48
-
-
-def sweep_call(rng):
-    """One call of the sweep: 1-6 rounds over 1-40 valid buckets (distinct
-    groups, each slot at most once, idle entries between), lengths 0..300, any
-    misalignment, sources shared / congruent / anywhere per entry-round.
-    Returns ids, groups, rounds and the round-major tables with both sizes."""
-    rounds = int(rng.integers(1, 7))
-    nb = int(rng.integers(1, 41))
-    groups = rng.permutation(SWEEP_GROUPS)[:nb].astype(np.uint32)
-    ids = _buckets(rng, groups)
-    n = ids.size
-    L = rng.integers(0, 301, rounds * n).astype(np.uint32)
-    L[rng.random(L.size) < 0.15] = 0
-    gap = rng.integers(1, 18, L.size).astype(np.uint64)
-    end = np.cumsum(L.astype(np.uint64) + gap)
-    doff = np.concatenate(([0], end[:-1])).astype(np.uint64) + np.uint64(rng.integers(0, 16))
-    order = rng.permutation(L.size)                      # spans of a slot's rounds lie anywhere, in any order
-    doff_p = np.empty_like(doff)
-    doff_p[order] = doff
-    L_p = np.empty_like(L)
-    L_p[order] = L
-    size = int(end[-1]) + 32
-    ssize = 4096 + 300
-    soff = (rng.random(L.size) * (ssize - L_p.astype(np.int64))).astype(np.uint64)
-    soff[rng.random(L.size) < 0.4] = int(rng.integers(0, 4096))
-    some = rng.random(L.size) < 0.3
-    adj = soff[some] + (doff_p[some] - soff[some]) % np.uint64(16)
-    ok = adj + L_p[some].astype(np.uint64) <= ssize
-    soff[np.flatnonzero(some)[ok]] = adj[ok]
-    return ids, groups, rounds, L_p, doff_p, size, soff, ssize
-
 
 @gpu
 def test_rounds_random_sweep(built, torch_cuda):
@@ -515,7 +381,7 @@ def test_rounds_random_sweep(built, torch_cuda):
     torch = torch_cuda
     rng = np.random.default_rng(9999)
     cap = SWEEP_GROUPS * 256
-    c, ob, T = _seeded(torch, 9998, cap)
+    c, ob, T = seeded(torch, 9998, cap)
     s = torch.cuda.current_stream()
     with c:
         for call in range(SWEEP_CALLS):
@@ -532,7 +398,7 @@ def test_rounds_random_sweep(built, torch_cuda):
                                       stream=s)
             c.sync(s)
             what = f"sweep call {call} ({n // 256} buckets x {rounds} rounds)"
-            _assert_equal(td.cpu().numpy(), want, what)
-            _assert_equal(ts.cpu().numpy(), src, what + ": source changed")
-            _check_states(c, ob, cap)
-        _check_continues(torch, c, ob, T, cap, rng)
+            assert_equal(td.cpu().numpy(), want, what)
+            assert_equal(ts.cpu().numpy(), src, what + ": source changed")
+            check_states(c, ob, cap)
+        check_continues(torch, c, ob, T, cap, rng)

@@ -10,41 +10,13 @@ import numpy as np
 import pytest
 
 import pyoracle
+from dispatch_model import claim_part
+from gpu_support import buckets, check_states, cu_count, dev, seeded
+from gpu_support import torch_cuda  # noqa: F401
 from zsummerx_amd import Context, ZRC4Error
 from zsummerx_amd._capi import IDLE_SLOT
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a GPU"
-    return torch
-
-
-def _seeded(torch, rng, cap):
-    keys = rng.integers(0, 256, 16 * cap, dtype=np.uint8)
-    koff = np.arange(cap, dtype=np.uint64) * 16
-    klen = np.full(cap, 16, dtype=np.uint32)
-    ob = pyoracle.Batch(cap)
-    ob.make_sbox(keys, koff, klen)
-    T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
-    c = Context(0, cap)
-    c.ksa_range(0, T(klen.view(np.int32)), T(koff.view(np.int64)), T(keys), stream=torch.cuda.current_stream())
-    return c, ob, T
-
-
-def _buckets(rng, groups, fill=(1, 256)):
-    """Bucket b: a random subset of group groups[b]'s slots in random entry
-    positions (IDLE_SLOT elsewhere); groups[b] == IDLE_SLOT: an idle bucket."""
-    ids = np.full(256 * len(groups), IDLE_SLOT, dtype=np.uint32)
-    for b, g in enumerate(groups):
-        if g == IDLE_SLOT:
-            continue
-        k = int(rng.integers(fill[0], fill[1] + 1))
-        ids[256 * b + rng.permutation(256)[:k]] = int(g) * 256 + rng.permutation(256)[:k]
-    return ids
 
 
 def _oracle_crypt(ob, data, ids, off, L, skip=()):
@@ -55,13 +27,6 @@ def _oracle_crypt(ob, data, ids, off, L, skip=()):
         pyoracle.lib().oracle_encryption(pyoracle.C.byref(ob.st[int(ids[e])]),
                                          pyoracle.C.c_void_p(want.ctypes.data + int(off[e])), int(L[e]))
     return want
-
-
-def _check_states(c, ob, cap):
-    gsb, gx, gy = c.get_states(0, cap)
-    osb, ox, oy = ob.states()
-    bad = np.flatnonzero((gsb != osb).any(axis=1) | (gx != ox) | (gy != oy))
-    assert bad.size == 0, bad[:8]
 
 
 @pytest.mark.parametrize("nb,trunc,idle", [(16, 0, 0), (27, 11, 0.2), (32, 0, 0), (100, 0, 0.1), (200, 5, 0.1),
@@ -78,14 +43,14 @@ def test_declared_bit_exact(built, torch_cuda, nb, trunc, idle):
     rng = np.random.default_rng(900 + nb + trunc)
     G = max(256, nb + 40)
     cap = 256 * G
-    c, ob, T = _seeded(torch, rng, cap)
+    c, ob, T = seeded(torch, rng, cap)
     s = torch.cuda.current_stream()
     with c:
         for call in range(2):
             groups = rng.permutation(G)[:nb].astype(np.uint32)
             if idle:
                 groups[:-1][rng.random(nb - 1) < idle] = IDLE_SLOT
-            ids = _buckets(rng, groups)
+            ids = buckets(rng, groups)
             if trunc:                                           # a short last bucket
                 ids = ids[:ids.size - trunc].copy()
             busy = ids != IDLE_SLOT
@@ -100,7 +65,7 @@ def test_declared_bit_exact(built, torch_cuda, nb, trunc, idle):
             got = pay.cpu().numpy()
             bad = np.flatnonzero(got != want)
             assert bad.size == 0, (call, bad[:8], int(bad.size))
-        _check_states(c, ob, cap)
+        check_states(c, ob, cap)
 
 
 @pytest.mark.parametrize("nb", [20, 100, 200, 700])
@@ -113,13 +78,13 @@ def test_declared_mismatch_is_refused(built, torch_cuda, nb):
     rng = np.random.default_rng(1200 + nb)
     G = max(256, nb + 40)
     cap = 256 * G
-    c, ob, T = _seeded(torch, rng, cap)
+    c, ob, T = seeded(torch, rng, cap)
     s = torch.cuda.current_stream()
     with c:
         perm = rng.permutation(G)
         groups = perm[:nb].astype(np.uint32)
         H, H2 = int(perm[nb]), int(perm[nb + 1])          # groups no bucket declares
-        ids = _buckets(rng, groups)
+        ids = buckets(rng, groups)
         ids[256 * 2: 256 * 3] = IDLE_SLOT
         ids[256 * 2 + rng.permutation(256)[:50]] = H * 256 + rng.permutation(256)[:50]
         groups[5] = IDLE_SLOT
@@ -139,7 +104,7 @@ def test_declared_mismatch_is_refused(built, torch_cuda, nb):
         got = pay.cpu().numpy()
         bad = np.flatnonzero(got != want)
         assert bad.size == 0, (bad[:8], int(bad.size))
-        _check_states(c, ob, cap)                            # H, H2 states unchanged (oracle skipped them)
+        check_states(c, ob, cap)                            # H, H2 states unchanged (oracle skipped them)
 
 
 @pytest.mark.parametrize("nb", [20, 100, 200, 700])
@@ -154,11 +119,11 @@ def test_declared_mismatch_blocks_named_group_above_window(built, torch_cuda, nb
     rng = np.random.default_rng(1300 + nb)
     G = max(256, nb + 40)
     cap = 256 * G
-    c, ob, T = _seeded(torch, rng, cap)
+    c, ob, T = seeded(torch, rng, cap)
     s = torch.cuda.current_stream()
     with c:
         groups = rng.permutation(G)[:nb].astype(np.uint32)
-        ids = _buckets(rng, groups, fill=(100, 200))
+        ids = buckets(rng, groups, fill=(100, 200))
         B = int(groups[7])
         ids[256 * 3: 256 * 4] = IDLE_SLOT                     # bucket 3 (declared groups[3]) names B's slots
         used7 = set(int(v) for v in ids[256 * 7: 256 * 8] if v != IDLE_SLOT)
@@ -182,14 +147,14 @@ def test_declared_mismatch_blocks_named_group_above_window(built, torch_cuda, nb
         want = _oracle_crypt(ob, data, keep, off, L)
         bad = np.flatnonzero(got != want)
         assert bad.size == 0, (bad[:8], int(bad.size))
-        _check_states(c, ob, cap)
+        check_states(c, ob, cap)
 
 
 def test_declared_argument_checks(built, torch_cuda):
     """A declared group past the arena is refused on the host (nothing
     launched); a NULL group array is refused."""
     torch = torch_cuda
-    T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    T = dev(torch)
     with Context(0, 1024) as c:
         ids = T(np.arange(256, dtype=np.int32))
         pay = T(np.zeros(256 * 8, dtype=np.uint8))
@@ -207,19 +172,6 @@ def test_declared_argument_checks(built, torch_cuda):
         assert pay.cpu().numpy()[:8].tobytes() == ks
 
 
-def _claim_part(nb, cus, j):
-    """The part of a group a declared launch of nb buckets claims for group
-    lane j (zrc4_kernels.hpp Claim): the window kernel (nb <= 32) claims the
-    dword column q = col(j) >> 2, the half-group kernel (2 nb <= CUs) and the
-    persistent kernel (nb > CUs, wave-pair halves) the half j >> 7, the
-    whole-group kernel the whole group (part 0)."""
-    if nb <= 32:
-        return (j & 31) | ((j >> 7) << 5)
-    if 2 * nb <= cus or nb > cus:
-        return j >> 7
-    return 0
-
-
 @pytest.mark.parametrize("nb", [20, 100, 200, 700])
 def test_declared_two_buckets_one_group(built, torch_cuda, nb):
     """two buckets of one declared launch both (correctly) declare
@@ -232,17 +184,17 @@ def test_declared_two_buckets_one_group(built, torch_cuda, nb):
     wave-pair half.  Every other bucket, and every state, matches the
     oracle."""
     torch = torch_cuda
-    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    cus = cu_count(torch)
     rng = np.random.default_rng(1400 + nb)
     G = max(256, nb + 40)
     cap = 256 * G
-    c, ob, T = _seeded(torch, rng, cap)
+    c, ob, T = seeded(torch, rng, cap)
     s = torch.cuda.current_stream()
     with c:
         groups = rng.permutation(G)[:nb].astype(np.uint32)
         A = int(groups[4])
         groups[9] = A                                          # bucket 9 declares A too
-        ids = _buckets(rng, groups)
+        ids = buckets(rng, groups)
         lanes = rng.permutation(256)
         for b, half in ((4, lanes[:128]), (9, lanes[128:])):  # disjoint slots of A, spread over every part
             ids[256 * b: 256 * (b + 1)] = IDLE_SLOT
@@ -274,7 +226,7 @@ def test_declared_two_buckets_one_group(built, torch_cuda, nb):
         parts = {}
         for e, r in ran.items():
             if r:
-                parts.setdefault(_claim_part(nb, cus, int(ids[e]) & 255), set()).add(e // 256)
+                parts.setdefault(claim_part(nb, cus, int(ids[e]) & 255), set()).add(e // 256)
         both = {p: bs for p, bs in parts.items() if len(bs) > 1}
         assert not both, f"parts crypted by both buckets: {both}"
         assert any(ran.values()), "one bucket runs each part it wins"
@@ -285,7 +237,7 @@ def test_declared_two_buckets_one_group(built, torch_cuda, nb):
         want = _oracle_crypt(ob, data, keep, off, L)
         bad = np.flatnonzero(got != want)
         assert bad.size == 0, (bad[:8], int(bad.size))
-        _check_states(c, ob, cap)
+        check_states(c, ob, cap)
 
 
 def pyoracle_batch_copy(ob, cap):
@@ -311,13 +263,13 @@ def test_declared_refused_bucket_frames_nothing(built, torch_cuda, nb):
     rng = np.random.default_rng(1500 + nb)
     G = max(256, nb + 40)
     cap = 256 * G
-    c, ob, T = _seeded(torch, rng, cap)
+    c, ob, T = seeded(torch, rng, cap)
     s = torch.cuda.current_stream()
     with c:
         perm = rng.permutation(G)
         groups = perm[:nb].astype(np.uint32)
         H, H2 = int(perm[nb]), int(perm[nb + 1])
-        ids = _buckets(rng, groups)
+        ids = buckets(rng, groups)
         ids[256 * 2: 256 * 3] = IDLE_SLOT
         ids[256 * 2 + rng.permutation(256)[:50]] = H * 256 + rng.permutation(256)[:50]
         groups[5] = IDLE_SLOT
@@ -362,4 +314,4 @@ def test_declared_refused_bucket_frames_nothing(built, torch_cuda, nb):
         for name, w, g in (("npk", w_npk, g_npk), ("used", w_used, g_used), ("status", w_st, g_st)):
             diff = np.flatnonzero(keep & (w != g))
             assert diff.size == 0, (name, diff[:8].tolist(), w[diff[:4]].tolist(), g[diff[:4]].tolist())
-        _check_states(c, ob, cap)
+        check_states(c, ob, cap)

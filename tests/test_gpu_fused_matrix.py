@@ -20,7 +20,9 @@ import numpy as np
 import pytest
 
 import pyoracle
-from test_frame_scan import BOUND, frame_report, payload_report
+from dispatch_model import kernel_class
+from frame_support import BOUND, frame_report, payload_report
+from gpu_support import cu_count, dev
 
 IDLE = 0xFFFFFFFF                       # ZRC4_IDLE_SLOT (include/zrc4.h)
 SENT = 0xA5A5A5A5                       # prefill of every framing output
@@ -195,22 +197,8 @@ def check_case(cs):
 
 
 # --------------------------------------------------------------- the matrix
-def kernel_class(mode, first_slot, groups, cus):
-    """launch_crypt's choice (zrc4.hip): the window kernel up to 32 aligned
-    groups, half-group workgroups while 2 G <= CUs, whole-group ones while
-    G <= CUs (an unaligned range: gathered columns on the whole-group
-    kernel), the persistent kernel above."""
-    aligned = mode == "grouped" or first_slot % 256 == 0
-    if groups <= 32 and aligned:
-        return "win"
-    if groups > cus:
-        return "stream"
-    if 2 * groups <= cus and aligned:
-        return "half"
-    return "whole"
-
-
-# id, entry point, first_slot, groups(cus), entries of the last group, class, kernel meant
+# id, entry point, first_slot, groups(cus), entries of the last group, class (kernel_class of
+# tests/dispatch_model.py), kernel meant
 MATRIX = [
     ("range_fs0_33g_half_kRange", "range", 0, lambda cus: 33, 77, "half", "crypt_half_kernel<kRange,true>"),
     ("range_fs0_halfCUs+1g_whole_kRange", "range", 0, lambda cus: cus // 2 + 1, 1, "whole",
@@ -335,7 +323,7 @@ def test_generator_builds_every_case(spec, seed, bound, maxp):
 def gpu():
     import torch
     assert torch.cuda.is_available(), "gpu tests need a GPU"
-    return torch, torch.cuda.get_device_properties(0).multi_processor_count
+    return torch, cu_count(torch)
 
 
 def _seed_arena(torch, lay, c1, seed):
@@ -351,7 +339,7 @@ def _seed_arena(torch, lay, c1, seed):
     klen = np.full(lay.cap, 16, np.uint32)
     ob = pyoracle.Batch(lay.cap)
     ob.make_sbox(keys.reshape(-1), koff, klen)
-    T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    T = dev(torch)
     c = Context(0, lay.cap)
     c.ksa_range(0, T(klen.view(np.int32)), T(koff.view(np.int64)), T(keys.reshape(-1)))
     c.sync()
@@ -361,7 +349,7 @@ def _seed_arena(torch, lay, c1, seed):
 def _launch(torch, c, lay, cs, with_pk=True):
     """One fused call over case cs; returns the payload and the framing
     outputs as the device left them (every output prefilled with SENT)."""
-    T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    T = dev(torch)
     n, maxp = cs.n, cs.maxp
     sent = lambda k: T(np.full(max(1, k), SENT, np.uint32).view(np.int32))
     npk, used, status, pk = sent(n), sent(n), sent(n), sent(n * maxp)

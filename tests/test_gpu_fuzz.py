@@ -21,6 +21,7 @@ import pytest
 
 import pyoracle
 from conftest import soak_seeds
+from gpu_support import dev
 from zsummerx_amd import Context
 from zsummerx_amd._capi import IDLE_SLOT
 
@@ -65,7 +66,7 @@ def _run_sequence(seed):
     klen = rng.integers(1, 17, cap).astype(np.uint32)
     ob = pyoracle.Batch(cap)
     ob.make_sbox(keys, koff, klen)
-    T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    T = dev(torch)
     s = torch.cuda.current_stream()
     seen = []
     with Context(0, cap) as c:
@@ -163,7 +164,7 @@ def test_ksa_soak(built, seed):
     ob = pyoracle.Batch(n)
     ob.make_sbox(keys, koff, klen)
     osb, ox, oy = ob.states()
-    T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    T = dev(torch)
     s = torch.cuda.current_stream()
     with Context(0, cap) as c:
         if rng.random() < 0.5:

@@ -18,98 +18,25 @@ buckets) and undeclared."""
 import numpy as np
 import pytest
 
-import pyoracle
-from zsummerx_amd import Context, ZRC4Error
+from gpu_support import FILL, LONG, SHORT, assert_equal, buckets, check_continues, layout, seeded, span_index
+from gpu_support import torch_cuda  # noqa: F401
+from zsummerx_amd import ZRC4Error
 from zsummerx_amd._capi import IDLE_SLOT
 
 pytestmark = pytest.mark.gpu
-
-FILL = 0xA5
-# the 16-byte units and the 2 KiB ring chunk of the window kernel
-LONG = np.array([0, 1, 15, 16, 17, 63, 64, 65, 2047, 2048, 2049, 4100], dtype=np.uint32)
-# head, blocks 0-3 of the A/B ping-pong, 16-byte pieces and the tail of the lane-per-stream kernels
-SHORT = np.array([0, 1, 15, 16, 17, 63, 64, 65, 127, 128, 129, 191, 192, 193, 250], dtype=np.uint32)
-TAIL = 24          # bytes per slot of the following crypt_range
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a GPU"
-    return torch
-
-
-def _seeded(torch, seed, cap):
-    rng = np.random.default_rng(seed)
-    keys = rng.integers(0, 256, 16 * cap, dtype=np.uint8)
-    koff = np.arange(cap, dtype=np.uint64) * 16
-    klen = np.full(cap, 16, dtype=np.uint32)
-    ob = pyoracle.Batch(cap)
-    ob.make_sbox(keys, koff, klen)
-    T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
-    c = Context(0, cap)
-    c.ksa_range(0, T(klen.view(np.int32)), T(koff.view(np.int64)), T(keys), stream=torch.cuda.current_stream())
-    return c, ob, T
-
-
-def _layout(L, shift):
-    """Spans in entry order, 1-3 guard bytes (cycling) between them, the first
-    at `shift`.  The gaps and either length list sum to an odd number of bytes
-    modulo 16 per cycle, so the start misalignment of every list position
-    walks through all of 0..15."""
-    gap = 1 + (np.arange(L.size, dtype=np.uint64) % 3)
-    end = np.cumsum(L.astype(np.uint64) + gap)
-    off = np.concatenate(([0], end[:-1])).astype(np.uint64) + np.uint64(shift)
-    return off, int(end[-1]) + shift + 16
-
-
-def _span_index(off, L):
-    """Indexes of every span byte."""
-    L = L.astype(np.int64)
-    start = np.cumsum(L) - L
-    return np.repeat(off.astype(np.int64) - start, L) + np.arange(int(L.sum()), dtype=np.int64)
 
 
 def _want(ob, cap, size, slots, off, L, base=None):
     """The expected buffer: `base` (default 0xA5 everywhere) with the oracle
     keystream of slot slots[i] in span i, the oracle advanced."""
     want = np.full(size, FILL, dtype=np.uint8) if base is None else base.copy()
-    want[_span_index(off, L)] = 0
+    want[span_index(off, L)] = 0
     so = np.zeros(cap, dtype=np.uint64)
     sl = np.zeros(cap, dtype=np.uint32)
     so[slots] = off
     sl[slots] = L
     ob.crypt(want, so, sl)
     return want
-
-
-def _check_states(c, ob, cap):
-    gsb, gx, gy = c.get_states(0, cap)
-    osb, ox, oy = ob.states()
-    bad = np.flatnonzero((gsb != osb).any(axis=1) | (gx != ox) | (gy != oy))
-    assert bad.size == 0, bad[:8]
-
-
-def _check_continues(torch, c, ob, T, cap, rng):
-    """crypt_range of TAIL random bytes per slot of the whole context goes on
-    where the oracle's streams are; then every state."""
-    s = torch.cuda.current_stream()
-    data = rng.integers(0, 256, cap * TAIL, dtype=np.uint8)
-    off = np.arange(cap, dtype=np.uint64) * TAIL
-    L = np.full(cap, TAIL, dtype=np.uint32)
-    want = data.copy()
-    ob.crypt(want, off, L)
-    pay = T(data)
-    c.crypt_range(0, pay, T(off.view(np.int64)), T(L.view(np.int32)), stream=s)
-    c.sync(s)
-    bad = np.flatnonzero(pay.cpu().numpy() != want)
-    assert bad.size == 0, ("following crypt_range", bad[:8] // TAIL, int(bad.size))
-    _check_states(c, ob, cap)
-
-
-def _assert_equal(got, want, what):
-    bad = np.flatnonzero(got != want)
-    assert bad.size == 0, (what, bad[:8], int(bad.size), got[bad[:8]], want[bad[:8]])
 
 
 # -- range ---------------------------------------------------------------------
@@ -121,11 +48,11 @@ def test_keystream_range_whole_groups(built, torch_cuda, groups):
     lens = LONG if groups <= 32 else SHORT
     n = 256 * groups
     cap = n + 256                                        # one group the call does not touch
-    c, ob, T = _seeded(torch, 5100 + groups, cap)
+    c, ob, T = seeded(torch, 5100 + groups, cap)
     s = torch.cuda.current_stream()
     with c:
         L = lens[np.arange(n) % lens.size]
-        off, size = _layout(L, groups % 16)
+        off, size = layout(L, groups % 16)
         # every length of the list meets every start misalignment
         pairs = set(zip((np.arange(n) % lens.size).tolist(), (off % 16).tolist()))
         assert len(pairs) == 16 * lens.size or n < 16 * lens.size, len(pairs)
@@ -133,8 +60,8 @@ def test_keystream_range_whole_groups(built, torch_cuda, groups):
         out = T(np.full(size, FILL, dtype=np.uint8))
         c.keystream_range(0, out, T(off.view(np.int64)), T(L.view(np.int32)), stream=s)
         c.sync(s)
-        _assert_equal(out.cpu().numpy(), want, "keystream_range")
-        _check_continues(torch, c, ob, T, cap, rng)
+        assert_equal(out.cpu().numpy(), want, "keystream_range")
+        check_continues(torch, c, ob, T, cap, rng)
 
 
 def test_keystream_range_unaligned_first_slot(built, torch_cuda):
@@ -143,42 +70,30 @@ def test_keystream_range_unaligned_first_slot(built, torch_cuda):
     torch = torch_cuda
     rng = np.random.default_rng(4400)
     first, n, cap = 3, 700, 1024
-    c, ob, T = _seeded(torch, 5400, cap)
+    c, ob, T = seeded(torch, 5400, cap)
     s = torch.cuda.current_stream()
     with c:
         L = SHORT[np.arange(n) % SHORT.size]
-        off, size = _layout(L, 7)
+        off, size = layout(L, 7)
         want = _want(ob, cap, size, first + np.arange(n), off, L)
         out = T(np.full(size, FILL, dtype=np.uint8))
         c.keystream_range(first, out, T(off.view(np.int64)), T(L.view(np.int32)), stream=s)
         c.sync(s)
-        _assert_equal(out.cpu().numpy(), want, "keystream_range first_slot=3")
-        _check_continues(torch, c, ob, T, cap, rng)
+        assert_equal(out.cpu().numpy(), want, "keystream_range first_slot=3")
+        check_continues(torch, c, ob, T, cap, rng)
 
 
 # -- grouped -------------------------------------------------------------------
-
-def _buckets(rng, groups):
-    """Bucket b: a random subset (1-256 slots) of group groups[b] in shuffled
-    entry positions, IDLE_SLOT elsewhere; groups[b] == IDLE_SLOT: an idle bucket."""
-    ids = np.full(256 * len(groups), IDLE_SLOT, dtype=np.uint32)
-    for b, g in enumerate(groups):
-        if g == IDLE_SLOT:
-            continue
-        k = int(rng.integers(1, 257))
-        ids[256 * b + rng.permutation(256)[:k]] = int(g) * 256 + rng.permutation(256)[:k]
-    return ids
-
 
 def _grouped_case(rng, nb, G, idle_bucket=True):
     groups = rng.permutation(G)[:nb].astype(np.uint32)
     if idle_bucket:
         groups[nb // 2] = IDLE_SLOT
-    ids = _buckets(rng, groups)
+    ids = buckets(rng, groups)
     # every entry has a span (idle entries too: theirs must stay 0xA5);
     # SHORT holds a zero, so some busy entries have len == 0
     L = SHORT[rng.integers(0, SHORT.size, ids.size)]
-    off, size = _layout(L, nb % 16)
+    off, size = layout(L, nb % 16)
     return groups, ids, L, off, size
 
 
@@ -189,7 +104,7 @@ def test_keystream_grouped(built, torch_cuda, nb, declared):
     rng = np.random.default_rng(4600 + nb + declared)
     G = nb + 8
     cap = 256 * G
-    c, ob, T = _seeded(torch, 5600 + nb, cap)
+    c, ob, T = seeded(torch, 5600 + nb, cap)
     s = torch.cuda.current_stream()
     with c:
         groups, ids, L, off, size = _grouped_case(rng, nb, G)
@@ -200,8 +115,8 @@ def test_keystream_grouped(built, torch_cuda, nb, declared):
         c.keystream_grouped(out, T(off.view(np.int64)), T(L.view(np.int32)), T(ids.view(np.int32)),
                             groups if declared else None, stream=s)
         c.sync(s)
-        _assert_equal(out.cpu().numpy(), want, "keystream_grouped")
-        _check_continues(torch, c, ob, T, cap, rng)
+        assert_equal(out.cpu().numpy(), want, "keystream_grouped")
+        check_continues(torch, c, ob, T, cap, rng)
 
 
 def _refused_spans_then_mask(got, off, L, entries):
@@ -222,7 +137,7 @@ def test_keystream_grouped_mixed_bucket_is_refused(built, torch_cuda, nb, declar
     rng = np.random.default_rng(4800 + nb + declared)
     G = nb + 8
     cap = 256 * G
-    c, ob, T = _seeded(torch, 5800 + nb, cap)
+    c, ob, T = seeded(torch, 5800 + nb, cap)
     s = torch.cuda.current_stream()
     with c:
         groups, ids, L, off, size = _grouped_case(rng, nb, G, idle_bucket=False)
@@ -230,7 +145,7 @@ def test_keystream_grouped_mixed_bucket_is_refused(built, torch_cuda, nb, declar
         e = 256 + int(np.flatnonzero(ids[256:512] != IDLE_SLOT)[0])
         ids[e] = H * 256 + 5
         L[256:512] = np.maximum(L[256:512], 1)           # every entry of the refused bucket has bytes to show
-        off, size = _layout(L, nb % 16)
+        off, size = layout(L, nb % 16)
         ran = ids != IDLE_SLOT
         ran[256:512] = False
         want = _want(ob, cap, size, ids[ran], off[ran], L[ran])
@@ -242,8 +157,8 @@ def test_keystream_grouped_mixed_bucket_is_refused(built, torch_cuda, nb, declar
         assert ei.value.code == -7                         # ZRC4_ERR_GROUP
         got = out.cpu().numpy()
         _refused_spans_then_mask(got, off, L, 256 + np.flatnonzero(ids[256:512] != IDLE_SLOT))
-        _assert_equal(got, want, "mixed bucket")
-        _check_continues(torch, c, ob, T, cap, rng)        # (states: the oracle skipped bucket 1's slots)
+        assert_equal(got, want, "mixed bucket")
+        check_continues(torch, c, ob, T, cap, rng)        # (states: the oracle skipped bucket 1's slots)
 
 
 @pytest.mark.parametrize("nb", [2, 200])
@@ -254,14 +169,14 @@ def test_keystream_grouped_id_out_of_range(built, torch_cuda, nb):
     rng = np.random.default_rng(4900 + nb)
     G = nb + 8
     cap = 256 * G
-    c, ob, T = _seeded(torch, 5900 + nb, cap)
+    c, ob, T = seeded(torch, 5900 + nb, cap)
     s = torch.cuda.current_stream()
     with c:
         groups, ids, L, off, size = _grouped_case(rng, nb, G, idle_bucket=False)
         e = int(np.flatnonzero(ids[:256] == IDLE_SLOT)[0]) if (ids[:256] == IDLE_SLOT).any() else 0
         ids[e] = cap + 77
         L[e] = 193
-        off, size = _layout(L, nb % 16)
+        off, size = layout(L, nb % 16)
         ran = (ids != IDLE_SLOT) & (ids < cap)
         want = _want(ob, cap, size, ids[ran], off[ran], L[ran])
         out = T(np.full(size, FILL, dtype=np.uint8))
@@ -271,8 +186,8 @@ def test_keystream_grouped_id_out_of_range(built, torch_cuda, nb):
         assert ei.value.code == -5                         # ZRC4_ERR_SLOT_RANGE
         got = out.cpu().numpy()
         assert (got[int(off[e]): int(off[e]) + 193] == FILL).all()
-        _assert_equal(got, want, "id out of range")
-        _check_continues(torch, c, ob, T, cap, rng)
+        assert_equal(got, want, "id out of range")
+        check_continues(torch, c, ob, T, cap, rng)
 
 
 # -- the destination is never read -----------------------------------------------
@@ -290,7 +205,7 @@ def test_destination_is_never_read(built, torch_cuda, kind, count):
     if kind == "range":
         ids = np.arange(256 * count, dtype=np.uint32)
         L = SHORT[np.arange(ids.size) % SHORT.size]
-        off, size = _layout(L, 5)
+        off, size = layout(L, 5)
         groups = None
     else:
         groups, ids, L, off, size = _grouped_case(rng, count, G)
@@ -299,7 +214,7 @@ def test_destination_is_never_read(built, torch_cuda, kind, count):
     spans = []
     s = torch.cuda.current_stream()
     for fill in fills:
-        c, ob, T = _seeded(torch, 6000 + count, cap)
+        c, ob, T = seeded(torch, 6000 + count, cap)
         with c:
             want = _want(ob, cap, size, ids[busy], off[busy], L[busy], base=fill)
             out = T(fill)
@@ -310,6 +225,6 @@ def test_destination_is_never_read(built, torch_cuda, kind, count):
                                     stream=s)
             c.sync(s)
             got = out.cpu().numpy()
-            _assert_equal(got, want, "pre-filled destination")
-            spans.append(got[_span_index(off[busy], L[busy])])
+            assert_equal(got, want, "pre-filled destination")
+            spans.append(got[span_index(off[busy], L[busy])])
     assert (spans[0] == spans[1]).all()

@@ -9,16 +9,11 @@ import numpy as np
 import pytest
 
 import pyoracle
+from gpu_support import buckets, dev
+from gpu_support import torch_cuda  # noqa: F401
 from zsummerx_amd import Context, RC4Encryption, ZRC4Error, synth
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a GPU"
-    return torch
 
 
 @pytest.fixture(scope="module")
@@ -87,7 +82,7 @@ def test_ksa_key_lengths_batched(built, torch_cuda):
     keys[::7] = 0
     ob = pyoracle.Batch(n)
     ob.make_sbox(keys, koff, klen)
-    T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    T = dev(torch)
     s = torch.cuda.current_stream()
     for ids in (None, rng.permutation(2 * n)[:n].astype(np.uint32)):
         with Context(0, 2 * n) as c:
@@ -367,7 +362,7 @@ def test_staged_path_ragged(built, torch_cuda, ids_kind):
     klen = np.full(n, 16, dtype=np.uint32)
     ob = pyoracle.Batch(n)
     ob.make_sbox(keys, koff, klen)
-    T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    T = dev(torch)
     ids = None if ids_kind == "range" else rng.permutation(n + 4000)[:n].astype(np.uint32)
     s = torch.cuda.current_stream()
     with Context(0, n + 4000) as c:
@@ -412,7 +407,7 @@ def test_direct_path_block_edges(built, torch_cuda, first_slot):
     klen = np.full(n, 16, dtype=np.uint32)
     ob = pyoracle.Batch(n)
     ob.make_sbox(keys, koff, klen)
-    T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    T = dev(torch)
     edges = [0, 1, 15, 16, 17, 63, 64, 65, 127, 128, 129, 191, 192, 193, 255, 256, 320, 1000, 1024, 0]
     s = torch.cuda.current_stream()
     with Context(0, first_slot + n) as c:
@@ -456,7 +451,7 @@ def test_window_path_ragged(built, torch_cuda, first_slot, n):
     klen = np.full(n, 16, dtype=np.uint32)
     ob = pyoracle.Batch(n)
     ob.make_sbox(keys, koff, klen)
-    T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    T = dev(torch)
     edges = [0, 1, 15, 16, 17, 31, 32, 33, 255, 256, 1023, 1024, 1025, 2047, 2048, 2049, 4095, 4096, 4097, 5000]
     s = torch.cuda.current_stream()
     cap = first_slot + -(-n // 256) * 256 + 256
@@ -512,7 +507,7 @@ def test_dispatch_boundaries_bit_exact(built, torch_cuda, first_slot, n):
     klen = np.full(n, 16, dtype=np.uint32)
     ob = pyoracle.Batch(n)
     ob.make_sbox(keys, koff, klen)
-    T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    T = dev(torch)
     s = torch.cuda.current_stream()
     with Context(0, first_slot + n + 256) as c:
         c.ksa_range(first_slot, T(klen.view(np.int32)), T(koff.view(np.int64)), T(keys), stream=s)
@@ -539,16 +534,9 @@ def test_dispatch_boundaries_bit_exact(built, torch_cuda, first_slot, n):
 def grouped_batch(rng, n_groups, groups_total, fill=(1, 256)):
     """Buckets of 256 entries: bucket b takes a random subset (random order)
     of group g_b's slots, groups drawn without repetition; padding entries
-    are ZRC4_IDLE_SLOT.  Returns (ids[n], member_index[n] or -1)."""
-    from zsummerx_amd._capi import IDLE_SLOT
-    groups = rng.permutation(groups_total)[:n_groups]
-    ids = np.full(256 * n_groups, IDLE_SLOT, dtype=np.uint32)
-    for b, g in enumerate(groups):
-        k = int(rng.integers(fill[0], fill[1] + 1))
-        slots = g * 256 + rng.permutation(256)[:k]
-        pos = rng.permutation(256)[:k]
-        ids[256 * b + pos] = slots
-    return ids
+    are ZRC4_IDLE_SLOT (buckets() of tests/gpu_support.py after the group
+    draw).  Returns ids[n]."""
+    return buckets(rng, rng.permutation(groups_total)[:n_groups], fill)
 
 
 @pytest.mark.parametrize("fill,nb,trunc,idle", [
@@ -578,7 +566,7 @@ def test_grouped_ids_bit_exact(built, torch_cuda, fill, nb, trunc, idle):
     klen = np.full(cap, 16, dtype=np.uint32)
     ob = pyoracle.Batch(cap)
     ob.make_sbox(keys, koff, klen)
-    T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    T = dev(torch)
     s = torch.cuda.current_stream()
     with Context(0, cap) as c:
         c.ksa_range(0, T(klen.view(np.int32)), T(koff.view(np.int64)), T(keys), stream=s)
@@ -627,7 +615,7 @@ def test_grouped_ids_mixed_bucket_is_refused(built, torch_cuda):
     or state touched) and reported as ZRC4_ERR_GROUP; other buckets run."""
     torch = torch_cuda
     from zsummerx_amd._capi import IDLE_SLOT
-    T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    T = dev(torch)
     s = torch.cuda.current_stream()
     with Context(0, 1024) as c:
         c.ksa_host([b"key-%d" % i for i in range(1024)], ids=np.arange(1024, dtype=np.uint32))
@@ -679,7 +667,7 @@ def test_grouped_cross_bucket_conflict_is_refused(built, torch_cuda, nb, variant
     klen = np.full(cap, 16, dtype=np.uint32)
     ob = pyoracle.Batch(cap)
     ob.make_sbox(keys, koff, klen)
-    T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    T = dev(torch)
     s = torch.cuda.current_stream()
     groups = rng.permutation(G)[:nb - 1]
     dup_a, dup_b = 3, nb - 2                           # buckets dup_a and dup_b both take group groups[dup_a]
@@ -757,7 +745,7 @@ def test_grouped_stream_refusals(built, torch_cuda, variant):
     klen = np.full(cap, 16, dtype=np.uint32)
     ob = pyoracle.Batch(cap)
     ob.make_sbox(keys, koff, klen)
-    T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    T = dev(torch)
     s = torch.cuda.current_stream()
     mixed, twice, past, zero_dup = 5, 301, 450, 77
     from zsummerx_amd import build
@@ -830,12 +818,11 @@ def _device_workload(ctx, w, torch, ids_mode="range"):
     e crypting session perm[e]'s payload (zrc4_crypt_grouped /
     zrc4_crypt_grouped_declared).  Every session is crypted once either way,
     so the ciphertext and the states are the same."""
-    dev = "cuda"
-    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    t = dev(torch)
     s = torch.cuda.current_stream()
     ctx.ksa(t(w.key_len.view(np.int32)), t(w.key_off.view(np.int64)), t(w.keys), stream=s)
-    scratch = torch.zeros(1000, dtype=torch.uint8, device=dev)
-    zero = torch.zeros(w.n, dtype=torch.int64, device=dev)
+    scratch = torch.zeros(1000, dtype=torch.uint8, device="cuda")
+    zero = torch.zeros(w.n, dtype=torch.int64, device="cuda")
     ctx.crypt(scratch, zero, t(w.adv.view(np.int32)), stream=s)   # pre-advance
     pay = t(w.payload)
     if ids_mode == "range":
@@ -916,7 +903,7 @@ def test_xor_ring_matches_numpy(ctx, torch_cuda):
             q = int(rid[i]) * cap + (int(pos[i]) + k) % cap
             want_pay[int(off[i]) + k] ^= want_ring[q]
             want_ring[q] = 0
-    T = lambda a: torch.from_numpy(a).to("cuda")
+    T = dev(torch)
     d_ring, d_pay = T(ring), T(pay)
     d_rid, d_pos, d_off, d_len = T(rid.view(np.int32)), T(pos.view(np.int32)), T(off.view(np.int64)), T(lens.view(np.int32))
     # one launch per ring generation (entries sharing a ring must not run in one launch)
@@ -941,7 +928,7 @@ def test_reservoir_round_trip(built, torch_cuda, where):
     data = rng.integers(0, 256, (S, total), dtype=np.uint8)
     want = np.stack([np.frombuffer(pyoracle.Rc4(keys[s]).encryption(data[s].tobytes()), np.uint8) for s in range(S)])
     if where == "device":
-        T = lambda a: torch.from_numpy(a).to("cuda")
+        T = dev(torch)
     else:       # the session engine's layout: tables and payload in pinned host memory
         T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).pin_memory()
     with Context(0, S) as c:
@@ -991,7 +978,7 @@ def test_window_tag_restart(built, torch_cuda):
     klen = np.full(n, 16, dtype=np.uint32)
     ob = pyoracle.Batch(n)
     ob.make_sbox(keys, koff, klen)
-    T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    T = dev(torch)
     s = torch.cuda.current_stream()
     with Context(0, 1024, lib=var) as c:
         c.ksa_range(0, T(klen.view(np.int32)), T(koff.view(np.int64)), T(keys), stream=s)

@@ -56,15 +56,15 @@ import numpy as np
 import pytest
 
 import pyoracle
+from dispatch_model import family
+from gpu_support import (FILL, SHORT, assert_equal, check_continues, check_states, cu_count, disjoint, layout, seeded,
+                         sources)
+from gpu_support import torch_cuda  # noqa: F401
 from zsummerx_amd import ZRC4Error
 from zsummerx_amd._capi import IDLE_SLOT
-from test_gpu_addressing import family
-from test_gpu_crypt_to import SHORT, _layout, _sources
-from test_gpu_crypt_to_rounds import _assert_equal, _check_continues, _check_states, _seeded, disjoint
 
 gpu = pytest.mark.gpu
 
-FILL = 0xA5
 FORMS = {"inplace": 0, "keystream": 1, "to": 2, "rounds": 3}       # CryptIo of zrc4_plan.hpp
 REGIMES = ("small", "half", "whole", "persistent")
 ROUNDS = 3
@@ -220,8 +220,8 @@ def build_call(rng, form, regime, declared, kinds, cap):
         idle = 256 * b + np.flatnonzero(ids[256 * b: 256 * b + 256] == IDLE_SLOT)
         L[:, idle[[1, -2]]] = 17
     L = L.reshape(-1)
-    doff, size = _layout(L, nb % 16)
-    soff, ssize = _sources(rng, L, doff)
+    doff, size = layout(L, nb % 16)
+    soff, ssize = sources(rng, L, doff)
     return SimpleNamespace(kinds=kinds, nb=nb, n=n, R=R, ids=ids, ids_fixed=fixed, groups=groups, groups_fixed=gfixed,
                            L=L, doff=doff, size=size, soff=soff, ssize=ssize, role=role)
 
@@ -344,13 +344,6 @@ def test_generator_breaks_the_contract_as_meant(form, regime, declared, cus):
 
 # ------------------------------------------------------------------ the GPU side
 
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a GPU"
-    return torch
-
-
 def _launch(c, form, declared, k, ids, groups, T, dst, src, s):
     bg = groups if declared else None
     off, L, tid = T(k.doff.view(np.int64)), T(k.L.view(np.int32)), T(ids.view(np.int32))
@@ -443,9 +436,9 @@ def _run(torch, c, ob, T, case, k, ids, groups, role, rng, expect, what):
         assert ((ranP[:, pair]).sum() + (~ranP[:, pair]).sum()) == R * pair.size
     # R's two spans and every idle entry's: untouched (zrc4.h:141-142, :191-192, :237-239); bystanders exact;
     # guards, and everything else outside the spans that ran: as they were (:190, :229)
-    _assert_equal(got, want, what)
-    _assert_equal(ts.cpu().numpy(), src, what + ": source changed")                # zrc4.h:228
-    _check_states(c, ob, cap)                        # refused buckets' slots keep their states (:121-123, :194, :242)
+    assert_equal(got, want, what)
+    assert_equal(ts.cpu().numpy(), src, what + ": source changed")                # zrc4.h:228
+    check_states(c, ob, cap)                        # refused buckets' slots keep their states (:121-123, :194, :242)
     return ranP
 
 
@@ -462,10 +455,10 @@ def test_refusals(built, torch_cuda, form, regime, declared):
     its breaks (ZRC4_ERR_GROUP), then repaired (ZRC4_ERR_SLOT_RANGE where R is
     in the call, else nothing), then every stream continued."""
     torch = torch_cuda
-    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    cus = cu_count(torch)
     case = build_case(form, regime, declared, cus)
     rng = np.random.default_rng(_seed(case))
-    c, ob, T = _seeded(torch, _seed(case) + 1, case.cap)
+    c, ob, T = seeded(torch, _seed(case) + 1, case.cap)
     with c:
         for i, k in enumerate(case.calls):
             assert family("declared" if declared else "grouped", 0, k.n, cus, FORMS[form]) == case.family
@@ -477,7 +470,7 @@ def test_refusals(built, torch_cuda, form, regime, declared):
             fixed_role[(k.role == NONE) & (k.ids_fixed < case.cap) & (k.ids == k.ids_fixed)] = NONE       # J
             _run(torch, c, ob, T, case, k, k.ids_fixed, k.groups_fixed, fixed_role, rng, -5 if "R" in k.kinds else 0,
                  what + ", repaired")
-        _check_continues(torch, c, ob, T, case.cap, rng)
+        check_continues(torch, c, ob, T, case.cap, rng)
 
 
 @gpu
@@ -489,7 +482,7 @@ def test_rounds_declared_idle_bucket_of_zero_lengths_is_refused(built, torch_cud
     of it written (it has none), its slot's state unchanged, every other bucket
     exact.  (On the host-split path the same bucket is idle: J in test_refusals.)"""
     torch = torch_cuda
-    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    cus = cu_count(torch)
     nb = n_buckets(regime, cus)
     case = SimpleNamespace(form="rounds", regime=regime, declared=True, cus=cus, cap=(nb + SPARE) * 256)
     rng = np.random.default_rng(88000 + nb)
@@ -500,9 +493,9 @@ def test_rounds_declared_idle_bucket_of_zero_lengths_is_refused(built, torch_cud
     b = nb // 2
     e = 256 * b + np.flatnonzero(k.ids[256 * b:][:256] != IDLE_SLOT)
     assert e.size == 1 and k.groups[b] == IDLE_SLOT and (k.L.reshape(k.R, k.n)[:, e] == 0).all()
-    c, ob, T = _seeded(torch, 88001 + nb, case.cap)
+    c, ob, T = seeded(torch, 88001 + nb, case.cap)
     with c:
         _run(torch, c, ob, T, case, k, k.ids, k.groups, k.role, rng, -7, f"declared idle, all lengths zero, {regime}")
         k.groups_fixed[b] = k.ids[e[0]] >> 8         # declared as what it names: a valid bucket with nothing to do
         _run(torch, c, ob, T, case, k, k.ids, k.groups_fixed, k.role, rng, 0, "the same, declared truly")
-        _check_continues(torch, c, ob, T, case.cap, rng)
+        check_continues(torch, c, ob, T, case.cap, rng)

@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 import pyoracle
+from gpu_support import torch_cuda  # noqa: F401
 from zsummerx_amd import Context, ZRC4Error
 from zsummerx_amd._capi import IDLE_SLOT
 
@@ -43,13 +44,6 @@ class World:
         self.xy = self.x.astype(np.uint16) | (self.y.astype(np.uint16) << 8)
         for a in (self.sb, self.x, self.y, self.xy):
             a.setflags(write=False)
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a GPU"
-    return torch
 
 
 @pytest.fixture(scope="module")
