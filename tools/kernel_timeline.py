@@ -13,6 +13,14 @@ bench.py does) is read back and summarised:
   epilogue   t3 - t2   x/y + image store, drained
   span       max t3 - min t0 over the launch; entry skew = spread of t0
 
+crypt_win_kernel also stamps the shader clock inside its prologue: when the
+image rows are back (the wait in front of the S-box unpack) and right before
+the first win_windows call.  With the wave's own clock rate (its chain's
+cycles over its chain's time) they split the prologue into
+
+  data_in    entry -> entry, x/y and image back
+  to_window  data back -> first window (unpack, LDS drain, loop entry)
+
   python tools/kernel_timeline.py --workloads cfg2,cfg3,65536x1024
 """
 from __future__ import annotations
@@ -30,6 +38,23 @@ ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
 
 SHAPES = {"cfg2": (4096, 1024), "cfg3": (65536, 256), "cfg4": (1024, 65536)}
+
+
+def prologue_split(rec: np.ndarray, mid: np.ndarray) -> dict:
+    """The two prologue segments of crypt_win_kernel in us and in shader
+    cycles (mid: cycles since stamp 0 at image-in and at the first window)."""
+    r = rec[:, :4].astype(np.float64) * 10.0 / 1000.0
+    c = rec[:, 4:].astype(np.float64)
+    ghz = (c[:, 2] - c[:, 1]) / np.maximum(r[:, 2] - r[:, 1], 1e-9) / 1e3
+    m = mid.astype(np.float64)
+    ok = (m[:, 0] > 0) & (m[:, 1] >= m[:, 0])
+    if not ok.any():
+        return {}
+    q = lambda a: {"min": round(float(a.min()), 3), "med": round(float(np.median(a)), 3),
+                   "p90": round(float(np.percentile(a, 90)), 3), "max": round(float(a.max()), 3)}
+    din, tow = m[ok, 0], m[ok, 1] - m[ok, 0]
+    return {"waves": int(ok.sum()), "data_in_cyc": q(din), "to_window_cyc": q(tow),
+            "data_in_us": q(din / ghz[ok] / 1e3), "to_window_us": q(tow / ghz[ok] / 1e3)}
 
 
 def summarise(rec: np.ndarray, waves: int, L: int) -> dict:
@@ -101,6 +126,9 @@ def main():
                     help="only the first k waves of every 256-session group get payload (len 0 for the rest): "
                          "the chain rate at k waves per CU")
     ap.add_argument("--define", action="append", default=[], help="extra -D for the timing build (NAME=V)")
+    ap.add_argument("--lib", default=None,
+                    help="a timing library built beforehand (zsummerx_amd/libzrc4_<LIB>.so, e.g. of another "
+                         "revision's sources) instead of a ZRC4_TIMING build of this tree")
     args = ap.parse_args()
     from zsummerx_amd import build
     defs = {"ZRC4_TIMING": "1"}
@@ -108,7 +136,7 @@ def main():
         k, _, v = d.partition("=")
         defs[k] = v or "1"
     name = "timing" + "".join(f"_{k}{v}" for k, v in sorted(defs.items()) if k != "ZRC4_TIMING")
-    path = build.build_variant(name, defs)
+    path = build.PKG / f"libzrc4_{args.lib}.so" if args.lib else build.build_variant(name, defs)
     if args.build_only:
         print("built", path)
         return
@@ -184,7 +212,12 @@ def main():
         rc = hip.hipMemcpy(C.c_void_p(hwid.ctypes.data), C.c_void_p(sink.value + 65536), C.c_size_t(hwid.nbytes), 2)
         if rc:
             raise SystemExit(f"hipMemcpy failed {rc}")
-        if S <= 32 * 256:        # crypt_win_kernel (<= 32 groups): one record per 4-stream workgroup
+        mid = np.zeros((1024, 2), dtype=np.uint32)
+        rc = hip.hipMemcpy(C.c_void_p(mid.ctypes.data), C.c_void_p(sink.value + 65536 + 8192), C.c_size_t(mid.nbytes), 2)
+        if rc:
+            raise SystemExit(f"hipMemcpy failed {rc}")
+        win = S <= 32 * 256
+        if win:                  # crypt_win_kernel (<= 32 groups): one record per 4-stream workgroup
             waves = S // 4
             act = np.ones(waves, dtype=bool)
         else:
@@ -193,6 +226,8 @@ def main():
         out[wl] = summarise(rec[:waves][act], int(act.sum()), L)
         out[wl]["active_waves_per_group"] = args.active_waves
         out[wl]["ids"] = args.ids
+        if win:
+            out[wl]["prologue_split"] = prologue_split(rec[:waves], mid[:waves])
         if args.placement:
             print(wl, "placement:", json.dumps(placement(rec[:waves], hwid[:waves], act, L)), flush=True)
         print(wl, json.dumps(out[wl]), flush=True)

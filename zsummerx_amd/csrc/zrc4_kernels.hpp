@@ -180,12 +180,22 @@ __device__ __forceinline__ uint32_t img_vo(uint32_t j)
 #endif
 struct Stamps {
     uint64_t r[4], c[4];
+    uint64_t m[2] = {0, 0};      // crypt_win_kernel: shader clock at image in, at the first window's start
 };
 __device__ __forceinline__ void stamp(Stamps &s, int i)
 {
 #if ZRC4_TIMING
     s.r[i] = __builtin_amdgcn_s_memrealtime();
     s.c[i] = __builtin_amdgcn_s_memtime();
+#endif
+}
+// crypt_win_kernel's two stamps inside the prologue (shader clock only): the
+// record keeps them as cycles since stamp 0, two uint32 at sink + 72 KiB +
+// 8 * (w & 1023), behind the HW_ID words.
+__device__ __forceinline__ void stamp_mid(Stamps &s, int i)
+{
+#if ZRC4_TIMING
+    s.m[i] = __builtin_amdgcn_s_memtime();
 #endif
 }
 // crypt_stream_kernel (ZRC4_TIMING): lane 0 of the first wave of each wave
@@ -235,6 +245,9 @@ __device__ __forceinline__ void stamps_out(const Stamps &s, uint8_t *sink, uint3
         uint32_t *w = reinterpret_cast<uint32_t *>(sink + 65536u + (wave & 1023u) * 8u);
         w[0] = hw;
         w[1] = xcc;
+        uint32_t *m = reinterpret_cast<uint32_t *>(sink + 65536u + 8192u + (wave & 1023u) * 8u);
+        m[0] = s.m[0] ? (uint32_t)(s.m[0] - s.c[0]) : 0u;
+        m[1] = s.m[1] ? (uint32_t)(s.m[1] - s.c[0]) : 0u;
     }
 #endif
 }

@@ -282,21 +282,61 @@ crypt_win_kernel(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy, const u
     uint32_t gclaim = 0;                                                   // kGrouped: the group claimed
     bool bad = false;                                                      // kGrouped: the bucket breaks the contract
     if constexpr (MODE == kRange) {
+        // every argument the prologue reads, in one scalar round trip at
+        // entry (left alone, the compiler fetches n first, branches on the
+        // idle column and only then fetches the pointers: two trips in a row
+        // before the first load can leave)
+        asm volatile("" ::"s"(arena), "s"(xy), "s"(first_slot), "s"(payload), "s"(off), "s"(len), "s"(n), "s"(sink),
+                     "s"(gridDim.x));
+        if constexpr (TO) asm volatile("" ::"s"(fr.src), "s"(fr.src_off));
+        // What the first window needs beside the loaded state: the stream's
+        // LDS bases, win_windows' lane constants, the first marker tag and the
+        // lane's unit offsets (the same expressions as further down and in
+        // win_windows, so each is computed once, here).
+        const uint32_t sb = (uint32_t)(uintptr_t)(Sb + b * 256u), mb = (uint32_t)(uintptr_t)(Mk + b * 256u),
+                       rb = (uint32_t)(uintptr_t)(Ring + b * kWinRing);
+        const uint32_t bitl = 1u << l, l1 = (l + 1) << 8, tag0 = (1u << 8) | (255u - l), pos0 = 16u * l;
+        // ZRC4_WIN_EARLY: the markers cleared and those constants in
+        // registers, placed behind the issue of the prologue's loads and ahead
+        // of the first wait for them (the empty asm pins the values there;
+        // without it the compiler computes them where they are first used,
+        // behind the wait for the image and in front of the first window).
+#define ZRC4_WIN_EARLY                                                                      \
+    do {                                                                                    \
+        _Pragma("unroll") for (int i = 0; i < 4; ++i)                                       \
+            reinterpret_cast<uint4 *>(Mk)[lane + 64 * i] = make_uint4(0, 0, 0, 0);         \
+        asm volatile("" ::"v"(sb), "v"(mb), "v"(rb), "v"(bitl), "v"(l1), "v"(tag0), "v"(pos0)); \
+        _Pragma("unroll") for (uint32_t u = 1; u < kWinUnits; ++u)                          \
+            asm volatile("" ::"v"(pos0 + 16u * kWinLanes * u));   /* the XOR pass's unit offsets */ \
+        __builtin_amdgcn_sched_barrier(0);                                                  \
+    } while (0)
         const uint32_t e = wg * kGroup + kb;
         ent = e;
         slot = first_slot + e;
         valid = e < n;
-        if (!__builtin_amdgcn_ballot_w64(valid)) return;                      // whole dword column idle
+        // The entry's length, offsets and x/y leave first and the four image
+        // rows right behind them, on every lane (a lane past the batch reads
+        // the batch's last entry -- a launch has n >= 1 -- and drops it) and
+        // ahead of the idle-column return, so that the kernel arguments are
+        // read in one scalar round trip and the loads that follow are counted
+        // from one block: vmcnt(5) for length and offset, then x/y, with the
+        // image in flight; then the image with the payload prefetch in flight.
+        const uint32_t ec = valid ? e : n - 1u;
+        const uint32_t Lq = len[ec];
+        O = off[ec];
+        if constexpr (TO) SO = fr.src_off[ec];
+        const uint16_t sq = xy[first_slot + ec];                              // (widened below, behind the wait)
+        __builtin_amdgcn_sched_barrier(0);
+        // (the group of an idle column holds a busy one: its image exists)
         const uint8_t *img = arena + (size_t)(slot >> 8) * kGroupBytes + 4u * q;
 #pragma unroll
         for (int r = 0; r < 4; ++r)
             rows[r] = *reinterpret_cast<const uint32_t *>(img + (size_t)(lane + 64u * r) * 256u);
-        if (valid) {
-            L = len[e];
-            O = off[e];
-            if constexpr (TO) SO = fr.src_off[e];
-        }
-        sxy = valid ? xy[slot] : 0u;
+        // everything that needs no loaded data, under that round trip
+        ZRC4_WIN_EARLY;
+        if (!__builtin_amdgcn_ballot_w64(valid)) return;                      // whole dword column idle: the loads are dropped
+        L = valid ? Lq : 0u;
+        sxy = valid ? (uint32_t)sq : 0u;
     } else {
         uint32_t *te = reinterpret_cast<uint32_t *>(Ring);                    // slot & 255 -> entry
         uint32_t *tl = te + 256;                                              // length
@@ -411,7 +451,11 @@ crypt_win_kernel(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy, const u
     const bool aligned = (((uintptr_t)msg | (uintptr_t)smsg) & 15u) == 0u;
 
     // The S-boxes into LDS (the wave's 4 streams share every dword of the
-    // image column) and the markers cleared.  kGrouped: before the payload
+    // image column).  kRange: the markers were cleared in ZRC4_WIN_EARLY, so
+    // this is the only work between the image's arrival and the first window; after
+    // the payload prefetch, which is issued on every lane from one basic
+    // block, so the wait for the image leaves exactly the prefetch in flight
+    // (s_waitcnt vmcnt(kWinUnits) in the ISA).  kGrouped: before the payload
     // prefetch, whose addresses come from the slot table (a second round
     // trip): with the prefetch issued first, the compiler's wait for the
     // image column (older, on a path the per-lane prefetch branches join)
@@ -426,9 +470,23 @@ crypt_win_kernel(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy, const u
                 Sb[s4 * 256u + kk] = v;                                                     \
             }                                                                               \
         }                                                                                   \
-        _Pragma("unroll") for (int i = 0; i < 4; ++i)                                       \
-            reinterpret_cast<uint4 *>(Mk)[lane + 64 * i] = make_uint4(0, 0, 0, 0);         \
+        if constexpr (MODE == kGrouped) {                                                   \
+            _Pragma("unroll") for (int i = 0; i < 4; ++i)                                   \
+                reinterpret_cast<uint4 *>(Mk)[lane + 64 * i] = make_uint4(0, 0, 0, 0);     \
+        }                                                                                   \
     } while (0)
+    // ZRC4_TIMING builds: the image's arrival (the empty asm makes the wave
+    // wait for the four rows, where the product's own wait for them stands)
+    // between stamps 0 and 1; the first window's start is stamped in the loop.
+#if ZRC4_TIMING
+#define ZRC4_WIN_STAMP_IN                                                                   \
+    do {                                                                                    \
+        asm volatile("" ::"v"(rows[0]), "v"(rows[1]), "v"(rows[2]), "v"(rows[3]));          \
+        stamp_mid(ts, 0);                                                                   \
+    } while (0)
+#else
+#define ZRC4_WIN_STAMP_IN (void)0
+#endif
     if constexpr (MODE == kGrouped) {
         if (bad) {
             claim_wait(cold);                                                 // (no load left in flight at exit)
@@ -440,26 +498,48 @@ crypt_win_kernel(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy, const u
             claim_wait(cold);
             return;
         }
+        ZRC4_WIN_STAMP_IN;
         ZRC4_WIN_FILL;
     }
 
-    // payload prefetch of chunk 0 (aligned messages: whole 16-byte units).
-    // kGrouped: issued before the claim's answer is waited for (reads of the
-    // caller's entries only; a refused bucket drops them), on every lane
-    // (units past the message read the lane's sink bytes) so that the
-    // compiler's wait for x/y below counts exactly and leaves the claim --
-    // issued right after, from asm -- in flight until the first XOR pass.
+    // payload prefetch of chunk 0 (aligned messages: whole 16-byte units), on
+    // every lane and without a branch, so that every lane issues kWinUnits
+    // loads and the compiler's waits around them count exactly.
+    // kRange: issued once the entry is in and while the image is in flight.
+    // The lane holds the whole units u < k of the chunk (k = 0: unaligned, or
+    // the message ends before the lane's first unit); unit u >= k reads unit
+    // k - 1 again, and a lane with k = 0 its 16 sink bytes, so no load leaves
+    // the span or the sink: one 64-bit select for the base, one min and one
+    // add per unit.  (base + 256 u for every u would read up to a chunk past
+    // the message's end, which nothing says is mapped.)  The XOR pass uses
+    // unit u only if it lies inside the chunk, which for chunk 0 is u < k.
+    // kGrouped: units past the message read the lane's sink bytes; issued
+    // before the claim's answer is waited for (reads of the caller's entries
+    // only; a refused bucket drops them), so that the compiler's wait for x/y
+    // below leaves the claim -- issued right after, from asm -- in flight
+    // until the first XOR pass.  (The grouped forms keep their prologue as it
+    // was: with the range form's moves the declared launch of 4 096 x 1 KiB
+    // got slower although its way to the first window got shorter, DESIGN.md
+    // section 4.1.)
     // KS: no prefetch, the span is never read (the compiler's wait for x/y
     // then precedes the claim, which claim_wait alone waits for).
     uint4 pre[kWinUnits];
-    if constexpr (!KS) {
+    if constexpr (!KS && MODE == kGrouped) {
 #pragma unroll
         for (uint32_t u = 0; u < kWinUnits; ++u) {
             const uint32_t pos = 16u * (l + kWinLanes * u);
-            if constexpr (MODE == kGrouped)
-                pre[u] = *reinterpret_cast<const uint4 *>(aligned && pos + 16u <= L ? smsg + pos : sink + 16u * lane);
-            else if (aligned && pos + 16u <= L)
-                pre[u] = *reinterpret_cast<const uint4 *>(smsg + pos);
+            pre[u] = *reinterpret_cast<const uint4 *>(aligned && pos + 16u <= L ? smsg + pos : sink + 16u * lane);
+        }
+    } else if constexpr (!KS) {
+        const uint32_t pos0 = 16u * l;
+        const bool any = aligned && pos0 + 16u <= L;
+        const uint32_t full = (L - pos0 - 16u) / (16u * kWinLanes);          // k - 1 (any), capped by the min below
+        const uint32_t last = any ? 16u * kWinLanes * full : 0u;
+        const uint8_t *base = any ? smsg + pos0 : sink + 16u * lane;
+#pragma unroll
+        for (uint32_t u = 0; u < kWinUnits; ++u) {
+            const uint32_t d = 16u * kWinLanes * u;
+            pre[u] = *reinterpret_cast<const uint4 *>(base + (d < last ? d : last));
         }
     }
     if constexpr (MODE == kGrouped) cold = claim_part_async(cl, gclaim, q, wg);
@@ -467,8 +547,16 @@ crypt_win_kernel(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy, const u
     uint8_t *S = Sb + b * 256u;
     uint32_t *M = Mk + b * 256u;
     uint8_t *R = Ring + b * kWinRing;
-    if constexpr (MODE != kGrouped) ZRC4_WIN_FILL;
+    if constexpr (MODE != kGrouped) {
+        // x + 1 and y in registers before the image is waited for
+        asm volatile("" ::"v"(((sxy & 0xFFu) + 1u) & 0xFFu), "v"(sxy >> 8));
+        __builtin_amdgcn_sched_barrier(0);
+        ZRC4_WIN_STAMP_IN;
+        ZRC4_WIN_FILL;
+    }
 #undef ZRC4_WIN_FILL
+#undef ZRC4_WIN_EARLY
+#undef ZRC4_WIN_STAMP_IN
     __syncthreads();                                 // (grouped: also the tables read before the ring is used)
     stamp(ts, 1);
 
@@ -485,6 +573,9 @@ crypt_win_kernel(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy, const u
             for (int i = 0; i < 4; ++i) reinterpret_cast<uint4 *>(Mk)[lane + 64 * i] = make_uint4(0, 0, 0, 0);
             w.v = (1u << 8) | (255u - l);
         }
+#if ZRC4_TIMING
+        if (c0 == 0u) stamp_mid(ts, 1);          // the first window's start
+#endif
         win_windows(w, rem, l, sb, mb, rb);
         if constexpr (MODE == kGrouped) {
             // The claim's answer is first needed here: nothing has been
