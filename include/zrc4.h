@@ -244,11 +244,14 @@ int zrc4_keystream_grouped(zrc4_ctx *ctx, const uint32_t *ids,
  *     spans untouched: the claim is answered before the first store, as in
  *     the in-place calls.
  * `src` and `dst` are device memory or coherent pinned host memory, at any
- * alignment.  An entry whose two addresses are congruent mod 16 moves 16-byte
- * units wherever the destination's alignment allows (the in-place walk, loads
- * from the source); any other entry is crypted byte by byte -- correct, and
- * much slower per entry, most of all into pinned host memory (DESIGN.md §14
- * has the numbers): keep sources congruent where it matters.  With at most one group or bucket per CU the kernels read
+ * alignment.  On the lane-per-stream kernels (more than 32 groups or buckets)
+ * and in the copy launch below every entry stores aligned 16-byte units
+ * wherever the destination's alignment allows (the in-place walk); an entry
+ * whose two addresses are not congruent mod 16 feeds them with 16-byte loads
+ * at unaligned source addresses, which touch exactly the source span's bytes.
+ * On the window kernel (at most 32) such an entry is crypted byte by byte, 16
+ * lanes storing 16 adjacent bytes (DESIGN.md §14 has the numbers of both).
+ * With at most one group or bucket per CU the kernels read
  * the sources themselves, in one launch.  With more (the persistent
  * throughput kernel, which has no out-of-place form) the call makes TWO
  * launches on `stream`: a short kernel that copies the source span of every
@@ -295,8 +298,9 @@ int zrc4_crypt_to_grouped(zrc4_ctx *ctx, const uint32_t *ids, const uint32_t *bu
  *     0xFFF00000: ZRC4_ERR_INVALID_ARG, nothing launched.  n == 0: ZRC4_OK.
  *     rounds == 1 is the existing call (forwarded to it).
  * Everything else is zrc4_crypt_to_*'s: device or coherent pinned memory at
- * any alignment, entry-rounds congruent mod 16 move 16-byte units and the
- * others go byte by byte, no capture into a replayed HIP graph, disjoint
+ * any alignment, every entry-round stores aligned 16-byte units (fed by
+ * unaligned loads where its two addresses are not congruent mod 16), no
+ * capture into a replayed HIP graph, disjoint
  * 256-slot groups for concurrent streams, faults latched for zrc4_sync.
  * Kernels: with at most one group or bucket per CU the call is ONE launch of
  * the half-group, whole-group or declared kernel -- at 32 groups and fewer

@@ -81,6 +81,10 @@ enum StatType {
     STAT_RC4_BYTES,      // bytes crypted
     STAT_RC4_NANOS,      // wall time inside Rc4Hooks::crypt
     STAT_RC4_FRAMED,     // receive blocks framed on the device (setDeviceFraming)
+    STAT_BCAST_CALLS,    // broadcastSessionData / broadcastAccepter calls
+    STAT_BCAST_SHARED,   // broadcast targets encrypted straight from the shared plaintext
+    STAT_BCAST_COPIED,   // broadcast targets that went through TcpSession::send
+    STAT_BCAST_JOINED,   // of the shared ones: the region lies behind bytes staged earlier in the iteration
     STAT_SIZE,
 };
 
@@ -179,6 +183,10 @@ private:
     SessionBlock *_sending = nullptr;
     unsigned int _sendingLen = 0;     // bytes of _sending already written
     bool _sendingCrypted = false;     // _sending holds wire bytes
+    // This iteration's broadcast region of _sending: [_bcastOff, _bcastOff +
+    // _bcastLen) is not staged, the flush encrypts it from _bcastSrc.
+    unsigned int _bcastOff = 0, _bcastLen = 0;
+    const char *_bcastSrc = nullptr;
     std::deque<SessionBlock *> _sendque;
     uint32_t _slotRead = 0xFFFFFFFFu, _slotWrite = 0xFFFFFFFFu;
     bool _bFirstRecvData = true;
@@ -225,6 +233,17 @@ public:
     TcpSessionPtr getTcpSession(SessionID sID);
 
     void sendSessionData(SessionID sID, const char *orgData, unsigned int orgDataLen);
+    // One message to many sessions.  Every wire carries exactly the bytes of a
+    // loop of sendSessionData in `ids` order (the reference's only way,
+    // session.cpp:533-538, 584-606).  The message is copied ONCE, into a
+    // pinned block; the iteration's flush encrypts it out of place into the
+    // _sending block of every target that can take it there (keyed, linked,
+    // nothing queued, its first broadcast of the iteration, and either an
+    // empty _sending or a staged, not yet encrypted one with _joinSmallBlock
+    // and room behind it), with Rc4Hooks::cryptBatch.  Every other target goes
+    // through TcpSession::send.
+    void broadcastSessionData(const SessionID *ids, size_t n, const char *data, unsigned int len);
+    void broadcastAccepter(AccepterID aID, const char *data, unsigned int len);   // every linked session of the accepter
     void kickSession(SessionID sID);
     void kickClientSession(AccepterID aID = InvalidAccepterID);
     void kickConnect(SessionID cID = InvalidSessionID);
@@ -276,6 +295,9 @@ private:
     std::vector<TcpSessionPtr> _sendBatch;    // sessions whose _sending is in this crypt
     std::vector<TcpSessionPtr> _closeList;
     std::vector<Rc4Span> _spans;
+    std::vector<Rc4ToSpan> _toSpans;          // the broadcast regions of _sendBatch
+    std::vector<SessionBlock *> _bcastBlocks; // shared plaintexts, held until the flush that consumes them ends
+    std::vector<SessionID> _bcastIds;         // broadcastAccepter's target list
     std::vector<Rc4Frame> _frames;            // parallel to _spans when framing on the device
     std::vector<int> _recvFrame;              // _recvBatch[i] -> its frame in _frames, or -1
     bool _deviceFraming = false;

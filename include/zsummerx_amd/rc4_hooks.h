@@ -22,8 +22,10 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
 #include <memory>
 #include <string>
+#include <vector>
 
 namespace zsummerx_amd {
 
@@ -49,6 +51,17 @@ struct Rc4Frame {
     uint32_t used = 0;                // bytes they cover
     uint32_t status = 0;              // 1 stopped on shortage, 2 on corruption
     uint32_t pkt[kMaxPackets] = {};   // the first min(npk, kMaxPackets) lengths
+};
+
+// One out-of-place encryption (a broadcast target): dst[k] = src[k] ^ the next
+// keystream byte of stream `slot` for k < len, advancing it by len bytes.  The
+// source is not written and may be shared by any number of spans; the
+// destination is not read.
+struct Rc4ToSpan {
+    uint32_t slot;
+    uint32_t len;
+    const uint8_t *src;   // src, dst inside memory returned by Rc4Hooks::allocBlocks
+    uint8_t *dst;
 };
 
 class Rc4Hooks {
@@ -79,6 +92,28 @@ public:
         (void)frames;
         (void)bound;
         return -1;   // ZRC4_ERR_INVALID_ARG
+    }
+    // crypt() over spans[0..n) -- cryptFrame() when `frames` is given (only
+    // when canFrame()) -- then every to[0..nTo).  A slot appears at most once
+    // in each list; a slot in both runs its in-place span first in keystream
+    // order.  Sources may be shared (one message for many sessions);
+    // destinations overlap nothing, neither each other nor a source nor a
+    // span.  This default serves any hooks that have only crypt(): a copy of
+    // each source into its destination and a second in-place crypt().  The
+    // device hooks read the shared source in place (rc4_hooks_device.cpp).
+    virtual int cryptBatch(const Rc4Span *spans, uint32_t n, const Rc4ToSpan *to, uint32_t nTo,
+                           Rc4Frame *frames /* may be null */, uint32_t bound)
+    {
+        if (n || !nTo) {
+            const int rc = frames ? cryptFrame(spans, n, frames, bound) : crypt(spans, n);
+            if (rc != 0 || !nTo) return rc;
+        }
+        std::vector<Rc4Span> second(nTo);
+        for (uint32_t i = 0; i < nTo; ++i) {
+            if (to[i].len) std::memcpy(to[i].dst, to[i].src, to[i].len);
+            second[i] = Rc4Span{to[i].slot, to[i].len, to[i].dst};
+        }
+        return crypt(second.data(), nTo);
     }
     // Implementation counters as one JSON object (diagnostics).
     virtual std::string stats() const { return "{}"; }

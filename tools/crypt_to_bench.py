@@ -9,7 +9,7 @@
 
   python tools/crypt_to_bench.py [--out profiles/crypt_to/crypt_to_bench.jsonl]
                                  [--reps 10] [--rounds 3] [--shapes 4x16384,...]
-                                 [--src-shift BYTES]
+                                 [--src-shift BYTES] [--parent-rev REV]
 
 Shapes (entries x bytes, every entry its own slot, whole groups): 4 x 16 KiB,
 4 096 x 16 KiB, 16 384 x 16 KiB, 65 536 x 4 KiB (the native out-of-place
@@ -19,9 +19,15 @@ sources (entry i reads its own span) and as a broadcast (every entry reads the
 same span), the sources in device memory, the destinations in device memory
 and in pinned host memory.  All spans are 16-byte aligned unless --src-shift
 moves every source span by that many bytes: with a shift that is no multiple
-of 16 every entry takes (b)'s byte path.
+of 16 every entry of (b) is non-congruent (unaligned 16-byte loads on the
+lane-per-stream kernels, the byte path on the window kernel).
 
-Per round the two variants are warmed up and timed alternately, rep by rep,
+--parent-rev REV adds (c): the same call through the library built from git
+revision REV (zsummerx_amd.build.build_variant("parent", {}, rev=REV); built
+beforehand where there is no history), alternated with the others, so that a
+kernel change is measured against its parent in one process.
+
+Per round the variants are warmed up and timed alternately, rep by rep,
 with HIP events around the variant's calls.  Each round reports a median per
 variant; the spread (max - min) of a variant's round medians is the yardstick
 for a difference between the two.
@@ -72,9 +78,11 @@ def main() -> None:
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--src-shift", type=int, default=0, help="bytes added to every source offset")
+    ap.add_argument("--parent-rev", default="", help="also time crypt_to through the library of this git revision")
     args = ap.parse_args()
     import torch
-    from zsummerx_amd import Context
+    from zsummerx_amd import Context, build
+    parent = build.build_variant("parent", {}, rev=args.parent_rev) if args.parent_rev else None
     out = Path(args.out)
     out.parent.mkdir(parents=True, exist_ok=True)
     s = torch.cuda.current_stream()
@@ -104,7 +112,7 @@ def main() -> None:
                     body = src[args.src_shift:]
                     dense = body if sources == "distinct" else body.expand(n, size)
                     dview = dst if sources == "distinct" else dst.view(n, size)
-                    with Context(0, cap) as ca, Context(0, cap) as cb:
+                    with Context(0, cap) as ca, Context(0, cap) as cb, Context(0, cap, lib=parent) as cp:
                         def copy_then_in_place():
                             dview.copy_(dense, non_blocking=True)
                             ca.crypt_grouped_declared(dst, d_off, d_len, d_ids, groups, n=m, stream=s)
@@ -112,10 +120,16 @@ def main() -> None:
                         def crypt_to():
                             cb.crypt_to_grouped(src, d_soff, dst, d_off, d_len, d_ids, groups, n=m, stream=s)
 
+                        def crypt_to_parent():
+                            cp.crypt_to_grouped(src, d_soff, dst, d_off, d_len, d_ids, groups, n=m, stream=s)
+
                         fns = {"copy_then_in_place": copy_then_in_place, "crypt_to": crypt_to}
+                        if parent:
+                            fns["crypt_to_parent"] = crypt_to_parent
                         rounds = [one_round(torch, fns, args.reps) for _ in range(args.rounds)]
                         ca.sync(s)
                         cb.sync(s)
+                        cp.sync(s)
                     med = {k: [round(r[k], 2) for r in rounds] for k in fns}
                     a, b = statistics.median(med["copy_then_in_place"]), statistics.median(med["crypt_to"])
                     rec = {"entries": n, "bytes_per_entry": size, "buckets": m // 256, "sources": sources,
@@ -129,6 +143,12 @@ def main() -> None:
                                                                  min(med["copy_then_in_place"]), 2),
                            "crypt_to_spread_us": round(max(med["crypt_to"]) - min(med["crypt_to"]), 2),
                            "crypt_to_over_copy_then_in_place": round(b / a, 3)}
+                    if parent:
+                        pm = med["crypt_to_parent"]
+                        rec.update({"parent_rev": args.parent_rev, "crypt_to_parent_round_medians_us": pm,
+                                    "crypt_to_parent_us": round(statistics.median(pm), 2),
+                                    "crypt_to_parent_spread_us": round(max(pm) - min(pm), 2),
+                                    "crypt_to_over_parent": round(b / statistics.median(pm), 3)})
                     line = json.dumps(rec)
                     print(line, flush=True)
                     fh.write(line + "\n")

@@ -15,6 +15,9 @@
 // launch over the spans per iteration) |
 // host:<lib> (a CPU RC4Encryption loaded from <lib> -- oracle/liboracle.so or
 // oracle/_ref/libzrc4_ref.so; tests and the CPU baseline only) | off.
+// --broadcast-tag T (server): a packet whose proto id is T is echoed to its
+// sender and then broadcast to every linked session of the accepter
+// (SessionManager::broadcastAccepter).
 // Prints one JSON line of counters.
 #include <dlfcn.h>
 #include <signal.h>
@@ -114,6 +117,7 @@ struct Args {
     bool deviceFraming = false;   // frame receive blocks in the decrypt launch (direct device hooks)
     int device = 0;
     unsigned ring = 65536;        // keystream reservoir bytes per slot (device hooks)
+    int broadcastTag = -1;        // server: a packet with this proto id is echoed, then broadcast to its accepter
 };
 
 double now()
@@ -183,6 +187,7 @@ static int run(int argc, char **argv)
         else if (k == "--device-framing") a.deviceFraming = true;
         else if (k == "--device") a.device = std::stoi(val());
         else if (k == "--ring") a.ring = (unsigned)std::stoul(val());
+        else if (k == "--broadcast-tag") a.broadcastTag = (int)(std::stoul(val()) & 0xFFFFu);
         else {
             std::fprintf(stderr, "unknown option %s\n", k.c_str());
             return 2;
@@ -213,6 +218,16 @@ static int run(int argc, char **argv)
     std::vector<std::vector<char>> expect;
 
     // ---- server side (CStressServerHandler)
+    // Echo; a packet whose 16-bit proto id is --broadcast-tag then goes to every
+    // linked session of its accepter, the sender included (whose _sending block
+    // holds the staged echo: the broadcast lands behind it).
+    OnBlockDispatch serve = [&](const TcpSessionPtr &s, const char *b, unsigned len) {
+        s->send(b, len);
+        uint16_t tag = 0;
+        if (a.broadcastTag >= 0 && len >= 8) std::memcpy(&tag, b + 6, 2);
+        if (a.broadcastTag >= 0 && len >= 8 && tag == (uint16_t)a.broadcastTag)
+            mgr.broadcastAccepter(s->getAcceptID(), b, len);
+    };
     unsigned short port = (unsigned short)a.port;
     if (a.mode == "loopback" || a.mode == "server") {
         AccepterID aID = mgr.addAccepter("127.0.0.1", (unsigned short)a.port);
@@ -220,7 +235,7 @@ static int run(int argc, char **argv)
         so._rc4TcpEncryption = a.key;
         so._openFlashPolicy = a.flashPolicy;
         so._maxSendListCount = 40000;                      // FrameStressMain.cpp:425
-        so._onRawPacketProc = [](const TcpSessionPtr &s, const char *b, unsigned len) { s->send(b, len); };
+        so._onRawPacketProc = serve;
         so._onSessionLinked = [&](const TcpSessionPtr &) { linked++; };
         so._onSessionClosed = [&](const TcpSessionPtr &) { closed++; };
         if (!mgr.openAccepter(aID)) {
@@ -240,7 +255,7 @@ static int run(int argc, char **argv)
             SessionOptions &po = mgr.getAccepterOptions(pID)._sessionOptions;
             po._rc4TcpEncryption.clear();
             po._maxSendListCount = 40000;
-            po._onRawPacketProc = [](const TcpSessionPtr &s, const char *b, unsigned len) { s->send(b, len); };
+            po._onRawPacketProc = serve;
             po._onSessionLinked = [&](const TcpSessionPtr &) { linked++; };
             po._onSessionClosed = [&](const TcpSessionPtr &) { closed++; };
             if (!mgr.openAccepter(pID)) {
@@ -327,12 +342,14 @@ static int run(int argc, char **argv)
         "\"rc4_calls\": %.0f, \"rc4_spans\": %.0f, \"rc4_bytes\": %.0f, \"rc4_ms\": %.3f, "
         "\"rc4_us_per_call\": %.3f, \"spans_per_call\": %.2f, \"rc4_gib_s_inside_hooks\": %.4f, "
         "\"recv_bytes\": %.0f, \"send_bytes\": %.0f, \"recv_packs\": %.0f, \"iterations\": %llu, "
-        "\"device_framed\": %.0f, \"mismatches\": %llu, \"linked\": %llu, \"closed\": %llu, \"hooks\": %s}\n",
+        "\"device_framed\": %.0f, \"bcast_calls\": %.0f, \"bcast_shared\": %.0f, \"bcast_copied\": %.0f, \"bcast_joined\": %.0f, "
+        "\"mismatches\": %llu, \"linked\": %llu, \"closed\": %llu, \"hooks\": %s}\n",
         a.mode.c_str(), mgr.rc4Hooks() ? mgr.rc4Hooks()->name() : "none", a.sessions, a.block, a.depth, dt,
         e1 - e0, (double)(e1 - e0) / dt, calls, d(STAT_RC4_SPANS), d(STAT_RC4_BYTES), d(STAT_RC4_NANOS) * 1e-6,
         calls > 0 ? d(STAT_RC4_NANOS) * 1e-3 / calls : 0.0, calls > 0 ? d(STAT_RC4_SPANS) / calls : 0.0,
         d(STAT_RC4_NANOS) > 0 ? d(STAT_RC4_BYTES) / (d(STAT_RC4_NANOS) * 1e-9) / 1073741824.0 : 0.0,
-        d(STAT_RECV_BYTES), d(STAT_SEND_BYTES), d(STAT_RECV_PACKS), iters, d(STAT_RC4_FRAMED), mismatches, linked, closed,
+        d(STAT_RECV_BYTES), d(STAT_SEND_BYTES), d(STAT_RECV_PACKS), iters, d(STAT_RC4_FRAMED),
+        d(STAT_BCAST_CALLS), d(STAT_BCAST_SHARED), d(STAT_BCAST_COPIED), d(STAT_BCAST_JOINED), mismatches, linked, closed,
         mgr.rc4Hooks() ? mgr.rc4Hooks()->stats().c_str() : "{}");
     std::fflush(stdout);
     return mismatches ? 3 : 0;

@@ -153,6 +153,11 @@ def build_test_tools(force: bool = False, sanitize: bool | str = False) -> Path:
                                  every byte checked against the oracle (GPU)
       tools/bin/hooks_check_emu  the same host logic over a CPU emulation of
                                  the zrc4 C-ABI (tests/cpp/emu_zrc4_hip.cpp)
+      tools/bin/hooks_bcast_check      Rc4Hooks::cryptBatch driven like the engine's
+                                 broadcast, the whole pool checked against
+                                 the oracle (GPU); _emu: over the emulation,
+                                 with its zrc4_crypt_to_grouped
+                                 (tests/cpp/emu_zrc4_crypt_to.cpp)
       tools/bin/frame_stress_emu the engine + device hooks over that emulation
       tools/bin/emu_declared_check  the emulation's declared-group refusals
                                  against the GPU's rules
@@ -177,6 +182,8 @@ def build_test_tools(force: bool = False, sanitize: bool | str = False) -> Path:
     chk = ROOT / "tests" / "cpp" / "hooks_check.cpp"
     emu = ROOT / "tests" / "cpp" / "emu_zrc4_hip.cpp"
     emu_ks = ROOT / "tests" / "cpp" / "emu_zrc4_keystream.cpp"    # zrc4_keystream_* over emu's public ABI
+    emu_to = ROOT / "tests" / "cpp" / "emu_zrc4_crypt_to.cpp"     # zrc4_crypt_to_grouped over emu's public ABI
+    bc_chk = ROOT / "tests" / "cpp" / "hooks_bcast_check.cpp"
     ks_chk = ROOT / "tests" / "cpp" / "emu_keystream_check.cpp"
     dev = ENGINE / "rc4_hooks_device.cpp"
     plan_chk = ROOT / "tests" / "cpp" / "plan_check.cpp"
@@ -189,18 +196,25 @@ def build_test_tools(force: bool = False, sanitize: bool | str = False) -> Path:
          ["g++", "-O2", *common, "-o", str(out / "hooks_check"), str(chk), *oracle_link,
           f"-L{PKG}", "-lzsx_frame", "-lzrc4", "-lpthread", "-Wl,-rpath,$ORIGIN/../../zsummerx_amd",
           f"-Wl,-rpath,{ROCM / 'lib'}"]),
-        (out / "hooks_check_emu", [chk, orc, emu, emu_ks] + FRAME_DEPS,
+        (out / "hooks_check_emu", [chk, orc, emu, emu_ks, emu_to] + FRAME_DEPS,
          ["g++", "-O2", *common, *emu_flags, "-o", str(out / "hooks_check_emu"), str(chk), str(dev), str(emu),
-          str(emu_ks), *oracle_link, "-lpthread"]),
+          str(emu_ks), str(emu_to), *oracle_link, "-lpthread"]),
+        (out / "hooks_bcast_check", [bc_chk, orc, frame] + FRAME_DEPS,
+         ["g++", "-O2", *common, "-o", str(out / "hooks_bcast_check"), str(bc_chk), *oracle_link,
+          f"-L{PKG}", "-lzsx_frame", "-lzrc4", "-lpthread", "-Wl,-rpath,$ORIGIN/../../zsummerx_amd",
+          f"-Wl,-rpath,{ROCM / 'lib'}"]),
+        (out / "hooks_bcast_check_emu", [bc_chk, orc, emu, emu_ks, emu_to] + FRAME_DEPS,
+         ["g++", "-O2", *common, *emu_flags, "-o", str(out / "hooks_bcast_check_emu"), str(bc_chk), str(dev), str(emu),
+          str(emu_ks), str(emu_to), *oracle_link, "-lpthread"]),
         (out / "emu_declared_check", [orc, emu, emu_ks, ROOT / "tests" / "cpp" / "emu_declared_check.cpp", ROOT / "include" / "zrc4.h"],
          ["g++", "-O2", *common, *emu_flags, "-o", str(out / "emu_declared_check"),
           str(ROOT / "tests" / "cpp" / "emu_declared_check.cpp"), str(emu), str(emu_ks), *oracle_link, "-lpthread"]),
         (out / "emu_keystream_check", [orc, emu, emu_ks, ks_chk, ROOT / "include" / "zrc4.h"],
          ["g++", "-O2", *common, *emu_flags, "-o", str(out / "emu_keystream_check"), str(ks_chk), str(emu),
           str(emu_ks), *oracle_link, "-lpthread"]),
-        (out / "frame_stress_emu", [orc, emu, emu_ks, ROOT / "tools" / "frame_stress.cpp"] + FRAME_DEPS,
+        (out / "frame_stress_emu", [orc, emu, emu_ks, emu_to, ROOT / "tools" / "frame_stress.cpp"] + FRAME_DEPS,
          ["g++", "-O2", *common, *emu_flags, "-o", str(out / "frame_stress_emu"), str(ROOT / "tools" / "frame_stress.cpp"),
-          *map(str, FRAME_SOURCES), str(emu), str(emu_ks), *oracle_link, "-ldl", "-lpthread"]),
+          *map(str, FRAME_SOURCES), str(emu), str(emu_ks), str(emu_to), *oracle_link, "-ldl", "-lpthread"]),
     ]
     # (an older tests/ tree run against this build has no reservoir_check.cpp
     # or plan_check.cpp and no test that asks for the binary: then there is
@@ -236,6 +250,20 @@ def build_mirror_bench(force: bool = False) -> Path:
     return out
 
 
+def build_bcast_bench(force: bool = False) -> Path:
+    """tools/bin/hooks_bcast_bench: one broadcast at the hooks interface, shared
+    source against copy-then-crypt (tools/hooks_bcast_bench.cpp)."""
+    frame = build_frame(force)
+    src = ROOT / "tools" / "hooks_bcast_bench.cpp"
+    out = ROOT / "tools" / "bin" / "hooks_bcast_bench"
+    out.parent.mkdir(parents=True, exist_ok=True)
+    if force or _stale(out, [src, frame] + FRAME_DEPS):
+        subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", f"-I{ROOT / 'include'}", "-o", str(out), str(src),
+                        f"-L{PKG}", "-lzsx_frame", "-lzrc4", "-lpthread", "-Wl,-rpath,$ORIGIN/../../zsummerx_amd",
+                        f"-Wl,-rpath,{ROCM / 'lib'}"], check=True)
+    return out
+
+
 def build_ubench(force: bool = False) -> None:
     """tools/ubench/traffic_calib: the known-byte-count kernels the PMC
     traffic passes calibrate FETCH_SIZE against (scripts/pmc_traffic.sh)."""
@@ -266,6 +294,7 @@ def build_all(force: bool = False) -> None:
     build_test_tools(force)
     build_ubench(force)
     build_mirror_bench(force)
+    build_bcast_bench(force)
 
 
 if __name__ == "__main__":

@@ -558,7 +558,8 @@ __device__ __forceinline__ void crypt_blocks_asm(Rc4Lane &st, uint4 *&p, uint32_
 // The out-of-place block loop (zrc4_crypt_to_*): crypt_blocks_asm with one
 // difference, the address of every load is the store pointer plus the lane's
 // 64-bit `delta` = source - destination (ZL_SRC_DELTA, one VALU add per
-// block; delta is a multiple of 16, so loads stay 16-byte aligned).  Loads,
+// block; stores are 16-byte aligned, loads are when delta is a multiple of 16
+// and at unaligned addresses otherwise, which global loads take).  Loads,
 // stores and every vmcnt count are crypt_blocks_asm's: four loads and four
 // stores per block.  On entry A holds (or is loading) block 0 OF THE SOURCE.
 // delta == 0 is exactly the in-place loop.
@@ -692,6 +693,14 @@ __device__ __forceinline__ void round_wait_asm(uint32_t &nl, uint64_t &no, uint6
     asm volatile("s_waitcnt vmcnt(0)" : "+v"(nl), "+v"(no), "+v"(ns) :: "memory");
 }
 
+// 16 bytes at any address (the out-of-place walks' source loads).
+typedef uint32_t u32x4_any __attribute__((ext_vector_type(4), aligned(1)));
+__device__ __forceinline__ uint4 load16_any(const void *p)
+{
+    const u32x4_any w = *static_cast<const u32x4_any *>(p);
+    return make_uint4(w[0], w[1], w[2], w[3]);
+}
+
 // Crypt one lane's message in place: unaligned head bytes, 64-byte blocks
 // (crypt_blocks_asm), 16-byte chunks, tail bytes.  If `pre` is set, A already
 // holds the first 64-byte block (issued by the caller ahead of the LDS fill).
@@ -699,25 +708,19 @@ __device__ __forceinline__ void round_wait_asm(uint32_t &nl, uint64_t &no, uint6
 // byte of msg (A and pre are unused).
 // kIoTo (zrc4_crypt_to_*): msg is the destination, and every load comes from
 // msg + delta (delta = source - destination, two's complement).  The walk is
-// set by the destination's alignment.  delta % 16 == 0: the same walk, with
-// 16-byte loads from the source (crypt_blocks_to_asm; `pre`: A holds the
-// source's first block).  Otherwise no 16-byte load of the source would be
-// aligned, and the whole message goes byte by byte (one byte load, one PRGA
-// step, one byte store): correct at any pair of alignments, about as fast as
-// the head and tail loops, and never a read of the destination.
+// set by the destination's alignment alone, at any delta: 16-byte loads from
+// the source (crypt_blocks_to_asm; `pre`: A holds the source's first block)
+// feed aligned 16-byte stores.  With delta % 16 != 0 those loads are at
+// unaligned addresses, which global loads take on this target (hipcc itself
+// emits global_load_dwordx4 for a 16-byte load through an aligned(1) type);
+// they cover exactly the source bytes of the units stored, nothing rounded to
+// a 16-byte unit of the source, and the destination is never read.
 // DRAIN (kIoTo in a rounds kernel): crypt_blocks_to_asm<true>.
 template <int IO = kIoInPlace, bool DRAIN = false>
 __device__ __forceinline__ void crypt_message(uint8_t *S, Rc4Lane &st, uint8_t *msg,
                                               uint32_t len, uint4 (&A)[4], bool pre, uint64_t delta = 0)
 {
     constexpr bool KS = IO == kIoKs, TO = IO == kIoTo;
-    if constexpr (TO) {
-        if (delta & 15u) {
-            const uint8_t *s = reinterpret_cast<const uint8_t *>((uintptr_t)msg + delta);
-            for (uint32_t i = 0; i < len; ++i) msg[i] = s[i] ^ (uint8_t)prga_step(S, st);
-            return;
-        }
-    }
     const uint32_t head = head_bytes(msg, len);
     for (uint32_t i = 0; i < head; ++i) {
         const uint8_t k = (uint8_t)prga_step(S, st);
@@ -744,7 +747,7 @@ __device__ __forceinline__ void crypt_message(uint8_t *S, Rc4Lane &st, uint8_t *
     uint32_t rem = len & 63u;
     while (rem >= 16u) {
         if constexpr (KS) *p = xor16(S, st, make_uint4(0u, 0u, 0u, 0u));
-        else if constexpr (TO) *p = xor16(S, st, *reinterpret_cast<const uint4 *>((uintptr_t)p + delta));
+        else if constexpr (TO) *p = xor16(S, st, load16_any(reinterpret_cast<const void *>((uintptr_t)p + delta)));
         else *p = xor16(S, st, *p);
         ++p;
         rem -= 16u;
@@ -1717,8 +1720,10 @@ crypt_body(uint8_t *__restrict__ arena, uint16_t *__restrict__ xy,
     if constexpr (TO) delta = (uint64_t)(uintptr_t)(fr.src + mysoff) - (uint64_t)(uintptr_t)msg;
     const uint8_t *blk0 = reinterpret_cast<const uint8_t *>((uintptr_t)msg + delta);
     // (KS stores keystream and loads no payload: there is no block 0 to issue;
-    // an out-of-place entry whose addresses are not congruent mod 16 goes byte
-    // by byte, crypt_message)
+    // an out-of-place entry whose addresses are not congruent mod 16 has its
+    // lead block issued by crypt_message, behind the fill: ahead of it the
+    // declared whole-group form had compiler writes to v41, v46 and v47 under
+    // the tracked load)
     // (ROUNDS issues every round's lead block inside its walk: ahead of the
     // fill the block would stay in flight across the code of the other lanes'
     // heads, pieces and tails, which hipcc gave v40..v47 to; the 64 keystream
@@ -3257,10 +3262,11 @@ span_fill_kernel(const uint32_t *__restrict__ ids, uint8_t *__restrict__ out, co
 // Skipped entries keep their destination bytes, exactly as in
 // span_fill_kernel; so does an entry whose source and destination are the
 // same address (the in-place case: nothing to copy).  One wave per entry,
-// grid-stride.  Addresses congruent mod 16: bytes up to the destination's first
-// 16-byte boundary, 16-byte units, tail bytes.  Otherwise bytes, 64 per wave
-// and step.  Loads from the source and stores to the destination only,
-// nothing outside [dst_off, dst_off + len).
+// grid-stride.  Bytes up to the destination's first 16-byte boundary, 16-byte
+// units (aligned stores; the loads are unaligned when the two addresses are
+// not congruent mod 16), tail bytes.  Loads from the source and stores to the
+// destination only, nothing outside [src_off, src_off + len) and
+// [dst_off, dst_off + len).
 // ---------------------------------------------------------------------------
 __global__ void __launch_bounds__(256)
 span_copy_kernel(const uint32_t *__restrict__ ids, const uint8_t *src, const uint64_t *__restrict__ src_off,
@@ -3275,16 +3281,12 @@ span_copy_kernel(const uint32_t *__restrict__ ids, const uint8_t *src, const uin
         uint8_t *p = dst + dst_off[e];
         const uint8_t *s = src + src_off[e];
         if (s == p) continue;
-        if (((uintptr_t)s ^ (uintptr_t)p) & 15u) {
-            for (uint32_t i = lane; i < L; i += 64u) p[i] = s[i];
-            continue;
-        }
         const uint32_t head = head_bytes(p, L);
         if (lane < head) p[lane] = s[lane];
         const uint32_t body = L - head, units = body >> 4, tail = body & 15u;
         uint4 *q = reinterpret_cast<uint4 *>(p + head);
-        const uint4 *sq = reinterpret_cast<const uint4 *>(s + head);
-        for (uint32_t u = lane; u < units; u += 64u) q[u] = sq[u];
+        const uint8_t *sq = s + head;
+        for (uint32_t u = lane; u < units; u += 64u) q[u] = load16_any(sq + 16u * (size_t)u);
         if (lane < tail) p[head + 16u * units + lane] = s[head + 16u * units + lane];
     }
 }

@@ -6,8 +6,10 @@
 //   2. accept / connect completions (both RC4 streams seeded, also on accept),
 //      recv into each session's _recving tail, resume partial sends;
 //   3. flushHooks(): every session with a staged _sending block merges its
-//      queue (session.cpp:579-601), then ONE Rc4Hooks::crypt covers every
-//      fresh recv tail and every staged _sending block of the iteration;
+//      queue (session.cpp:579-601), then ONE Rc4Hooks::cryptBatch covers every
+//      fresh recv tail and every staged _sending block of the iteration in
+//      place, and every broadcast region out of place from its shared
+//      plaintext (broadcastSessionData);
 //      encrypted blocks are written to their sockets, decrypted tails go
 //      through the proto4z framing loop and dispatch (session.cpp:326-467);
 //   4. closes requested during the iteration are finished.
@@ -648,7 +650,10 @@ void SessionManager::flushHooks()
     for (TcpSessionPtr &sp : _dirtyList) {
         TcpSession &s = *sp;
         s._dirty = false;
-        if (s._status != 2 || s._closing) continue;
+        if (s._status != 2 || s._closing) {
+            s._bcastLen = 0;
+            continue;
+        }
         if (s._sending->len == 0 && !s._sendque.empty()) {
             do {
                 SessionBlock *sb = s._sendque.front();
@@ -691,21 +696,33 @@ void SessionManager::flushHooks()
             _frames.push_back(f);
         }
     }
+    _toSpans.clear();
     for (TcpSessionPtr &sp : _sendBatch) {
         TcpSession &s = *sp;
         if (s._options._rc4TcpEncryption.empty()) continue;
-        _spans.push_back({s._slotWrite, s._sending->len, reinterpret_cast<uint8_t *>(s._sending->begin)});
+        // A broadcast region (always the block's end) is encrypted out of place
+        // from the shared plaintext; the staged bytes before it in place, and
+        // first in the slot's keystream.
+        const unsigned int inPlace = s._bcastLen ? s._bcastOff : s._sending->len;
+        if (s._bcastLen) {
+            _toSpans.push_back({s._slotWrite, s._bcastLen, reinterpret_cast<const uint8_t *>(s._bcastSrc),
+                                reinterpret_cast<uint8_t *>(s._sending->begin + s._bcastOff)});
+            s._bcastLen = 0;
+        }
+        if (inPlace == 0) continue;
+        _spans.push_back({s._slotWrite, inPlace, reinterpret_cast<uint8_t *>(s._sending->begin)});
         if (devFrame) _frames.emplace_back();
     }
-    if (!_spans.empty()) {
+    if (!_spans.empty() || !_toSpans.empty()) {
         const auto t0 = std::chrono::steady_clock::now();
-        const int rc = devFrame ? hooks()->cryptFrame(_spans.data(), (uint32_t)_spans.size(), _frames.data(),
-                                                      SESSION_BLOCK_SIZE)
-                                : hooks()->crypt(_spans.data(), (uint32_t)_spans.size());
+        const int rc = hooks()->cryptBatch(_spans.data(), (uint32_t)_spans.size(), _toSpans.data(),
+                                           (uint32_t)_toSpans.size(), devFrame ? _frames.data() : nullptr,
+                                           SESSION_BLOCK_SIZE);
         const auto t1 = std::chrono::steady_clock::now();
         _statInfo[STAT_RC4_CALLS]++;
-        _statInfo[STAT_RC4_SPANS] += _spans.size();
+        _statInfo[STAT_RC4_SPANS] += _spans.size() + _toSpans.size();
         for (const Rc4Span &sp : _spans) _statInfo[STAT_RC4_BYTES] += sp.len;
+        for (const Rc4ToSpan &sp : _toSpans) _statInfo[STAT_RC4_BYTES] += sp.len;
         _statInfo[STAT_RC4_NANOS] +=
             (unsigned long long)std::chrono::duration_cast<std::chrono::nanoseconds>(t1 - t0).count();
         if (rc != ZRC4_OK) {
@@ -728,6 +745,8 @@ void SessionManager::flushHooks()
         writeSending(sp);
     }
     _sendBatch.clear();
+    for (SessionBlock *sb : _bcastBlocks) FreeBlock(sb);      // every region that read them is encrypted
+    _bcastBlocks.clear();
     for (size_t r = 0; r < _recvBatch.size(); ++r) {
         TcpSessionPtr &sp = _recvBatch[r];
         sp->_recvFresh = 0;
@@ -832,6 +851,58 @@ void SessionManager::sendSessionData(SessionID sID, const char *orgData, unsigne
 {
     TcpSessionPtr s = getTcpSession(sID);
     if (s) s->send(orgData, orgDataLen);
+}
+
+void SessionManager::broadcastSessionData(const SessionID *ids, size_t n, const char *data, unsigned int len)
+{
+    _statInfo[STAT_BCAST_CALLS]++;
+    // The shared plaintext: one pinned block (its begin is congruent mod 64
+    // with every _sending->begin, so the kernels move 16-byte units), made
+    // when the first target takes the shared path.
+    SessionBlock *shared = nullptr;
+    for (size_t i = 0; i < n; ++i) {
+        TcpSessionPtr sp = getTcpSession(ids[i]);
+        if (!sp) continue;
+        TcpSession &s = *sp;
+        const bool staged = s._sending && s._sending->len != 0 && !s._sendingCrypted;
+        if (len == 0 || len > SESSION_BLOCK_SIZE || s._options._rc4TcpEncryption.empty() || s._status != 2 ||
+            s._closing || !s._sending || !s._sendque.empty() || s._bcastLen != 0 ||
+            (s._sending->len != 0 &&
+             !(staged && s._options._joinSmallBlock && s._sending->bound - s._sending->len >= len))) {
+            s.send(data, len);
+            _statInfo[STAT_BCAST_COPIED]++;
+            continue;
+        }
+        if (!shared) {
+            shared = CreateBlock();
+            std::memcpy(shared->begin, data, len);
+            shared->len = len;
+            _bcastBlocks.push_back(shared);
+        }
+        // The region joins _sending at once, so later sends of the iteration
+        // queue behind it (TcpSession::send); its bytes arrive in the flush.
+        s._bcastOff = s._sending->len;
+        s._bcastLen = len;
+        s._bcastSrc = shared->begin;
+        s._sending->len += len;
+        if (!staged) {
+            s._sendingLen = 0;
+            s._sendingCrypted = false;
+        }
+        _statInfo[STAT_SEND_PACKS]++;
+        _statInfo[STAT_BCAST_SHARED]++;
+        if (staged) _statInfo[STAT_BCAST_JOINED]++;
+        markDirty(s);
+    }
+}
+
+void SessionManager::broadcastAccepter(AccepterID aID, const char *data, unsigned int len)
+{
+    _bcastIds.clear();
+    for (auto &kv : _sessions)
+        if (isSessionID(kv.first) && kv.second->_acceptID == aID && kv.second->_status == 2)
+            _bcastIds.push_back(kv.first);
+    broadcastSessionData(_bcastIds.data(), _bcastIds.size(), data, len);
 }
 
 void SessionManager::kickSession(SessionID sID)

@@ -14,7 +14,9 @@
 // entries sorted by slot, one
 // 256-entry bucket per 256-slot group touched, so each bucket moves its
 // group's S-boxes as one coalesced 64 KiB image whatever subset of the group
-// the iteration touches (the kIds gather path is never used here).
+// the iteration touches (the kIds gather path is never used here).  The
+// out-of-place spans of cryptBatch (one shared plaintext for many sessions)
+// are a zrc4_crypt_to_grouped batch of the same layout.
 //
 // Two modes:
 //   direct     one grouped launch per engine iteration over the spans
@@ -114,6 +116,16 @@ int launchKeystream(zrc4_ctx *ctx, const Table &t, uint8_t *base, hipStream_t s)
                                   t.len.p, t.n, s);
 }
 
+// The out-of-place launch of cryptBatch over table t (its off = the
+// destinations) with the sources' offsets in soff, declared as launchGrouped
+// declares.  Above one bucket per CU the library makes it a copy launch and the
+// in-place crypt (include/zrc4.h).
+int launchTo(zrc4_ctx *ctx, const Table &t, const uint64_t *soff, uint8_t *base, hipStream_t s)
+{
+    return zrc4_crypt_to_grouped(ctx, t.ids.p, t.groups.size() <= 256u ? t.groups.data() : nullptr, base, soff, base,
+                                 t.off.p, t.len.p, t.n, s);
+}
+
 struct Entry {
     uint32_t slot;
     uint32_t len;
@@ -121,6 +133,7 @@ struct Entry {
     uint32_t idx = 0;     // the caller's span index (framed calls)
     uint32_t flen = 0;    // frame block length (framed calls)
     uint64_t foff = 0;    // frame block offset from the base (framed calls)
+    uint64_t soff = 0;    // source offset from the base (out-of-place entries)
 };
 
 // Per-entry framing tables of a framed grouped launch (pinned).
@@ -169,12 +182,32 @@ void xorBytes(uint8_t *__restrict dst, const uint8_t *__restrict src, size_t n)
     for (; i < n; ++i) dst[i] ^= src[i];
 }
 
+// dst = in ^ src for n bytes (dst is only written: it overlaps neither).
+void xorBytesTo(uint8_t *__restrict dst, const uint8_t *__restrict in, const uint8_t *__restrict src, size_t n)
+{
+    size_t i = 0;
+    for (; i + 8 <= n; i += 8) {
+        uint64_t a, b;
+        std::memcpy(&a, in + i, 8);
+        std::memcpy(&b, src + i, 8);
+        a ^= b;
+        std::memcpy(dst + i, &a, 8);
+    }
+    for (; i < n; ++i) dst[i] = in[i] ^ src[i];
+}
+
 // One piece of a reservoir call's host work: span bytes ^= committed ring
-// bytes.
+// bytes, or with `in` (an out-of-place span) dst = in ^ committed ring bytes.
 struct XorJob {
     uint8_t *dst;
     const uint8_t *src;
     uint32_t n;
+    const uint8_t *in = nullptr;
+    void run() const
+    {
+        if (in) xorBytesTo(dst, in, src, n);
+        else xorBytes(dst, src, n);
+    }
 };
 
 // The reservoir's host XOR for large batches, spread over worker threads.
@@ -213,7 +246,7 @@ public:
     void run(const std::vector<XorJob> &jobs, size_t bytes)
     {
         if (!workers_ || bytes < minBytes_ || jobs.size() < 2) {
-            for (const XorJob &j : jobs) xorBytes(j.dst, j.src, j.n);
+            for (const XorJob &j : jobs) j.run();
             return;
         }
         // contiguous job ranges of about equal bytes, one per thread
@@ -240,7 +273,7 @@ private:
     void work(unsigned part)
     {
         const std::vector<XorJob> &jobs = *jobs_;
-        for (size_t i = bounds_[part]; i < bounds_[part + 1]; ++i) xorBytes(jobs[i].dst, jobs[i].src, jobs[i].n);
+        for (size_t i = bounds_[part]; i < bounds_[part + 1]; ++i) jobs[i].run();
     }
     void loop(unsigned part)
     {
@@ -278,7 +311,7 @@ public:
         bool ok = hipSetDevice(device) == hipSuccess &&
                   hipStreamCreateWithFlags(&sA_, hipStreamNonBlocking) == hipSuccess &&
                   hipStreamCreateWithFlags(&sB_, hipStreamNonBlocking) == hipSuccess;
-        tt_.flags = hostAllocFlags();
+        tt_.flags = to_.flags = hostAllocFlags();
         if (ok && ringCap_) {
             // $ZSX_REFILL_CHUNK (A/B knob): bytes per slot per refill, at most a
             // quarter of the ring (two refills in flight leave half of it readable)
@@ -293,6 +326,7 @@ public:
             throw std::runtime_error("makeDeviceRc4Hooks: HIP stream/event creation failed");
         }
         seen_.assign(zrc4_capacity(ctx_), 0u);
+        seenTo_.assign(zrc4_capacity(ctx_), 0u);
     }
     ~DeviceRc4Hooks() override { release(); }
 
@@ -331,18 +365,60 @@ public:
         int rc = flushSeeds();
         if (rc != ZRC4_OK) return rc;
         if (n == 0) return ZRC4_OK;
-        // Each slot at most once per call (rc4_hooks.h contract): a second span
-        // of one slot would consume keystream the first already accounted for.
-        if (++callStamp_ == 0) {
-            std::fill(seen_.begin(), seen_.end(), 0u);
-            callStamp_ = 1;
-        }
-        for (uint32_t i = 0; i < n; ++i) {
-            const uint32_t s = spans[i].slot;
-            if (s >= seen_.size() || seen_[s] == callStamp_) return ZRC4_ERR_INVALID_ARG;
-            seen_[s] = callStamp_;
-        }
+        if (!markOnce(seen_, spans, n)) return ZRC4_ERR_INVALID_ARG;
         return ringCap_ ? cryptReservoir(spans, n) : cryptDirect(spans, n);
+    }
+
+    // The engine's broadcast call (rc4_hooks.h).  Direct mode: the grouped,
+    // optionally framed, launch over `spans`, then ONE out-of-place grouped
+    // launch over `to` on the same stream -- stream order is the keystream
+    // order of a slot in both lists -- and one wait.  Two launches rather than
+    // the two-round call: at 32 buckets and fewer the one-round calls keep
+    // the window kernel (include/zrc4.h).  Reservoir mode: cryptReservoir.
+    int cryptBatch(const Rc4Span *spans, uint32_t n, const Rc4ToSpan *to, uint32_t nTo, Rc4Frame *frames,
+                   uint32_t bound) override
+    {
+        if (nTo == 0) return frames ? cryptFrame(spans, n, frames, bound) : crypt(spans, n);
+        if (frames && ringCap_) return ZRC4_ERR_INVALID_ARG;
+        int rc = flushSeeds();
+        if (rc != ZRC4_OK) return rc;
+        if (!markOnce(seen_, spans, n) || !markOnce(seenTo_, to, nTo, false)) return ZRC4_ERR_INVALID_ARG;
+        toSpans_ += nTo;
+        for (uint32_t i = 0; i < nTo; ++i) toBytes_ += to[i].len;
+        if (ringCap_) return cryptReservoir(spans, n, to, nTo);
+
+        if (frames && n) {
+            if ((rc = launchFramed(spans, n, frames, bound)) != ZRC4_OK) return rc;
+        } else {
+            es_.clear();
+            for (uint32_t i = 0; i < n; ++i)
+                if (spans[i].len) es_.push_back({spans[i].slot, spans[i].len, offOf(spans[i].data)});
+            for (const Entry &e : es_) tailBytes_ += e.len;
+            if (!es_.empty()) {
+                buildGrouped(tt_, es_);
+                if ((rc = launchGrouped(ctx_, tt_, res_.base, nullptr, sA_)) != ZRC4_OK) return rc;
+                ++tailLaunches_;
+            }
+        }
+        eo_.clear();
+        for (uint32_t i = 0; i < nTo; ++i) {
+            if (!to[i].len) continue;
+            Entry e{to[i].slot, to[i].len, offOf(to[i].dst)};
+            e.soff = offOf(to[i].src);
+            eo_.push_back(e);
+            tailBytes_ += e.len;
+        }
+        if (!eo_.empty()) {
+            buildGroupedTo(to_, eo_, toSrc_);
+            if ((rc = launchTo(ctx_, to_, toSrc_.p, res_.base, sA_)) != ZRC4_OK) {
+                (void)zrc4_sync(ctx_, sA_);      // the in-place launch still runs over the caller's blocks
+                return rc;
+            }
+            ++tailLaunches_;
+        }
+        if ((rc = zrc4_sync(ctx_, sA_)) != ZRC4_OK) return rc;
+        if (frames && n) collectFrames(frames);
+        return ZRC4_OK;
     }
 
     // Device framing rides on the direct mode's launch (the reservoir mode
@@ -355,16 +431,58 @@ public:
         int rc = flushSeeds();
         if (rc != ZRC4_OK) return rc;
         if (n == 0) return ZRC4_OK;
-        if (++callStamp_ == 0) {
+        if (!markOnce(seen_, spans, n)) return ZRC4_ERR_INVALID_ARG;
+        if ((rc = launchFramed(spans, n, frames, bound)) != ZRC4_OK) return rc;
+        if ((rc = zrc4_sync(ctx_, sA_)) != ZRC4_OK) return rc;
+        collectFrames(frames);
+        return ZRC4_OK;
+    }
+
+    std::string stats() const override
+    {
+        char b[1024];
+        std::snprintf(b, sizeof b,
+                      "{\"ring_bytes\": %llu, \"tail_bytes\": %llu, \"tail_launches\": %llu, "
+                      "\"refill_bytes\": %llu, \"refill_launches\": %llu, \"refill_waits\": %llu, "
+                      "\"ring_cap\": %u, \"refill_chunk\": %u, \"device_framed\": %llu, \"xor_threads\": %u, "
+                      "\"direct_calls\": %llu, \"direct_bytes\": %llu, \"keystream_launches\": %llu, "
+                      "\"to_spans\": %llu, \"to_bytes\": %llu}",
+                      (unsigned long long)res_.coveredBytes, tailBytes_, tailLaunches_,
+                      (unsigned long long)res_.committedBytes, (unsigned long long)res_.launches,
+                      (unsigned long long)res_.waits, ringCap_, refillChunk_, framed_, xor_.threads(), directCalls_,
+                      (unsigned long long)directBytes_, (unsigned long long)res_.launches,   // (every refill is a keystream launch)
+                      toSpans_, toBytes_);
+        return b;
+    }
+
+private:
+    // Each slot at most once per list (rc4_hooks.h contract): a second span
+    // of one slot would consume keystream the first already accounted for.
+    // `seen` then holds callStamp_ at the slots of v[0..n).
+    // (cryptBatch marks its second list under the first one's stamp: fresh = false)
+    template <class S>
+    bool markOnce(std::vector<uint32_t> &seen, const S *v, uint32_t n, bool fresh = true)
+    {
+        if (fresh && ++callStamp_ == 0) {
             std::fill(seen_.begin(), seen_.end(), 0u);
+            std::fill(seenTo_.begin(), seenTo_.end(), 0u);
             callStamp_ = 1;
         }
+        for (uint32_t i = 0; i < n; ++i) {
+            const uint32_t s = v[i].slot;
+            if (s >= seen.size() || seen[s] == callStamp_) return false;
+            seen[s] = callStamp_;
+        }
+        return true;
+    }
+
+    // The framed grouped launch of cryptFrame on A (no wait), and its results
+    // after the wait.
+    int launchFramed(const Rc4Span *spans, uint32_t n, const Rc4Frame *frames, uint32_t bound)
+    {
         es_.clear();
         for (uint32_t i = 0; i < n; ++i) {
-            const uint32_t s = spans[i].slot;
-            if (s >= seen_.size() || seen_[s] == callStamp_) return ZRC4_ERR_INVALID_ARG;
-            seen_[s] = callStamp_;
-            Entry e{s, spans[i].len, offOf(spans[i].data)};
+            Entry e{spans[i].slot, spans[i].len, offOf(spans[i].data)};
             e.idx = i;
             e.flen = frames[i].len;
             e.foff = frames[i].len ? offOf(frames[i].block) : 0;
@@ -374,10 +492,12 @@ public:
         buildGrouped(tt_, es_, &ft_);
         zrc4_frame_args fa{ft_.off.p, ft_.len.p, bound, Rc4Frame::kMaxPackets, ft_.npk.p, ft_.used.p,
                            ft_.status.p, ft_.pkt.p};
-        rc = launchGrouped(ctx_, tt_, res_.base, &fa, sA_);
-        if (rc != ZRC4_OK) return rc;
-        ++tailLaunches_;
-        if ((rc = zrc4_sync(ctx_, sA_)) != ZRC4_OK) return rc;
+        const int rc = launchGrouped(ctx_, tt_, res_.base, &fa, sA_);
+        if (rc == ZRC4_OK) ++tailLaunches_;
+        return rc;
+    }
+    void collectFrames(Rc4Frame *frames)
+    {
         for (uint32_t b = 0; b < tt_.n; ++b) {
             const int64_t i = ft_.idx[b];
             if (i < 0 || !frames[i].len) continue;
@@ -389,25 +509,19 @@ public:
             std::memcpy(f.pkt, ft_.pkt.p + (size_t)b * Rc4Frame::kMaxPackets, k * sizeof(uint32_t));
             ++framed_;
         }
-        return ZRC4_OK;
     }
 
-    std::string stats() const override
+    // The grouped layout over out-of-place entries: t.off holds the
+    // destinations, soff the sources (padding reads nothing: length 0).
+    static void buildGroupedTo(Table &t, std::vector<Entry> &es, PinnedArray<uint64_t> &soff)
     {
-        char b[768];
-        std::snprintf(b, sizeof b,
-                      "{\"ring_bytes\": %llu, \"tail_bytes\": %llu, \"tail_launches\": %llu, "
-                      "\"refill_bytes\": %llu, \"refill_launches\": %llu, \"refill_waits\": %llu, "
-                      "\"ring_cap\": %u, \"refill_chunk\": %u, \"device_framed\": %llu, \"xor_threads\": %u, "
-                      "\"direct_calls\": %llu, \"direct_bytes\": %llu, \"keystream_launches\": %llu}",
-                      (unsigned long long)res_.coveredBytes, tailBytes_, tailLaunches_,
-                      (unsigned long long)res_.committedBytes, (unsigned long long)res_.launches,
-                      (unsigned long long)res_.waits, ringCap_, refillChunk_, framed_, xor_.threads(), directCalls_,
-                      (unsigned long long)directBytes_, (unsigned long long)res_.launches);   // (every refill is a keystream launch)
-        return b;
+        const bool ok = zrc4::buildGrouped(t, es, [&](const Entry *e) {
+            soff.reserve(t.n);
+            soff.p[t.n - 1] = e ? e->soff : 0;
+        });
+        if (!ok) throw std::bad_alloc();
     }
 
-private:
     uint64_t offOf(const void *p)
     {
         if (!res_.base) res_.base = static_cast<uint8_t *>(const_cast<void *>(p));
@@ -446,32 +560,49 @@ private:
     // what its ring holds, then its spans go to the device as tails, which
     // is exactly the direct mode's launch -- and below half of it refills
     // resume.  The keystream order is the same either way.
-    void updateMode(const Rc4Span *spans, uint32_t n)
+    void updateMode(const Rc4Span *spans, uint32_t n, const Rc4ToSpan *to, uint32_t nTo)
     {
         uint64_t bytes = 0;
         for (uint32_t i = 0; i < n; ++i) bytes += spans[i].len;
+        for (uint32_t i = 0; i < nTo; ++i) bytes += to[i].len;
         emaBytes_ = emaBytes_ == 0.0 ? (double)bytes : 0.875 * emaBytes_ + 0.125 * (double)bytes;
         if (directBytes_ && !direct_ && emaBytes_ >= (double)directBytes_) direct_ = true;
         else if (direct_ && emaBytes_ < 0.5 * (double)directBytes_) direct_ = false;
         if (direct_) ++directCalls_;
     }
 
-    int cryptReservoir(const Rc4Span *spans, uint32_t n)
+    // The spans in place, then (cryptBatch) the out-of-place spans `to`, whose
+    // keystream follows their slot's in-place span: dst = src ^ ring on the
+    // host, and what the ring does not cover is copied to dst and joins the
+    // device tail in place.
+    int cryptReservoir(const Rc4Span *spans, uint32_t n, const Rc4ToSpan *to = nullptr, uint32_t nTo = 0)
     {
-        updateMode(spans, n);
+        updateMode(spans, n, to, nTo);
         int rc = pollRefills(false);
         if (rc != ZRC4_OK) return rc;
-        rc = res_.waitCovered(n, [&](uint32_t i) { return std::pair<uint32_t, uint32_t>(spans[i].slot, spans[i].len); },
-                              zrc4::NoFaults());
+        if (nTo) {
+            // slotAux_[slot], at the slots of `spans` (seen_ holds the stamp):
+            // the in-place length here, the slot's tail entry below
+            slotAux_.resize(seen_.size());
+            for (uint32_t i = 0; i < n; ++i) slotAux_[spans[i].slot] = spans[i].len;
+        }
+        rc = res_.waitCovered(n + nTo, [&](uint32_t i) {
+            if (i < n) return std::pair<uint32_t, uint32_t>(spans[i].slot, spans[i].len);
+            const Rc4ToSpan &t = to[i - n];
+            const uint64_t need = (uint64_t)t.len + (seen_[t.slot] == callStamp_ ? slotAux_[t.slot] : 0u);
+            return std::pair<uint32_t, uint32_t>(t.slot, (uint32_t)std::min<uint64_t>(need, 0xFFFFFFFFu));
+        }, zrc4::NoFaults());
         if (rc != ZRC4_OK) return rc;
         // Host XOR with the committed ring bytes (XorPool, after this pass:
         // before any refill is launched, since a refill may write the ring
         // bytes consumed here); collect the uncovered tails.
         es_.clear();
+        eo_.clear();
         xj_.clear();
         size_t xjBytes = 0;
         for (uint32_t i = 0; i < n; ++i) {
             const Rc4Span &sp = spans[i];
+            if (nTo) slotAux_[sp.slot] = 0;
             if (!sp.len) continue;
             const uint32_t tail = res_.cover(sp.slot, sp.len, [&](uint32_t done, const uint8_t *q, uint32_t k) {
                 xj_.push_back({sp.data + done, q, k});
@@ -480,15 +611,40 @@ private:
             if (tail) {
                 // the slot's device state is at the end of what the ring covered
                 es_.push_back({sp.slot, tail, offOf(sp.data + (sp.len - tail))});
+                if (nTo) slotAux_[sp.slot] = (uint32_t)es_.size();
                 res_.afterTail(sp.slot, tail);
                 tailBytes_ += tail;
             }
             if (!direct_) res_.markHungry(sp.slot);
         }
+        for (uint32_t i = 0; i < nTo; ++i) {
+            const Rc4ToSpan &t = to[i];
+            if (!t.len) continue;
+            const uint32_t tail = res_.cover(t.slot, t.len, [&](uint32_t done, const uint8_t *q, uint32_t k) {
+                xj_.push_back({t.dst + done, q, k, t.src + done});
+            });
+            xjBytes += t.len - tail;
+            if (tail) {
+                uint8_t *d = t.dst + (t.len - tail);
+                std::memcpy(d, t.src + (t.len - tail), tail);
+                // A slot whose in-place span left a tail too (its ring is then
+                // empty: this whole span is tail) may appear once per launch:
+                // one entry where the two are adjacent, as a block's staged
+                // bytes and the broadcast behind them are; else a second launch.
+                const uint32_t k = seen_[t.slot] == callStamp_ ? slotAux_[t.slot] : 0u;
+                if (!k) es_.push_back({t.slot, tail, offOf(d)});
+                else if (es_[k - 1].off + es_[k - 1].len == offOf(d)) es_[k - 1].len += tail;
+                else eo_.push_back({t.slot, tail, offOf(d)});
+                res_.afterTail(t.slot, tail);
+                tailBytes_ += tail;
+            }
+            if (!direct_) res_.markHungry(t.slot);
+        }
         xor_.run(xj_, xjBytes);
-        if (!es_.empty()) {
+        if (!es_.empty() || !eo_.empty()) {
             if ((rc = drainRefills()) != ZRC4_OK) return rc;     // slot state must be quiet
             if ((rc = runTail(es_)) != ZRC4_OK) return rc;
+            if ((rc = runTail(eo_)) != ZRC4_OK) return rc;
         }
         while (!direct_ && !debugNoRefill_ && res_.inflight() < refillDepth_) {
             const uint32_t before = res_.inflight();
@@ -590,12 +746,15 @@ private:
     zrc4::Reservoir res_;                         // (its base is the payload base of every launch here)
     uint32_t ringCap_;
     uint32_t refillChunk_ = 0;
-    std::vector<uint32_t> seen_;
+    std::vector<uint32_t> seen_, seenTo_;         // call stamps per slot: the spans, cryptBatch's out-of-place spans
+    std::vector<uint32_t> slotAux_;               // per-slot scratch of a reservoir cryptBatch
     uint32_t callStamp_ = 0;
     std::vector<XorJob> xj_;
     XorPool xor_;
-    std::vector<Entry> es_;
+    std::vector<Entry> es_, eo_;
     Table tt_;                                    // tail grouped table
+    Table to_;                                    // out-of-place grouped table (cryptBatch, direct mode)
+    PinnedArray<uint64_t> toSrc_;                 // its source offsets
     FrameTable ft_;                               // framing tables of cryptFrame
     PinnedArray<uint32_t> kIds_, kLen_;
     PinnedArray<uint64_t> kOff_;
@@ -603,7 +762,7 @@ private:
     std::vector<uint32_t> seedIds_, seedLen_;
     std::vector<uint64_t> seedOff_;
     std::vector<uint8_t> keyBytes_;
-    unsigned long long tailBytes_ = 0, tailLaunches_ = 0, framed_ = 0;
+    unsigned long long tailBytes_ = 0, tailLaunches_ = 0, framed_ = 0, toSpans_ = 0, toBytes_ = 0;
 };
 
 }  // namespace
