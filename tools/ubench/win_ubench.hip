@@ -3,7 +3,7 @@
 // steps per iteration.  Checks every keystream byte and final state against a
 // serial CPU PRGA and reports cycles per byte per stream.
 //   build: hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/ubench/win_ubench.hip -o tools/ubench/win_ubench
-//   run:   tools/ubench/win_ubench [streams] [bytes] [W=8|16] [waves_per_block]
+//   run:   tools/ubench/win_ubench [streams] [bytes] [W=8|16] [waves_per_block] [mode[,mode...]]
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdint>
@@ -19,6 +19,7 @@
 #include "win_repair.hpp"
 #include "win_var2.hpp"
 #include "win_var3.hpp"
+#include "win_var4.hpp"
 #define CHECK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %s line %d\n", hipGetErrorString(e_), __LINE__); exit(1); } } while (0)
 
 constexpr int MAXN = (int)zrc4::kWinRing;   // keystream ring per stream (bytes)
@@ -903,6 +904,48 @@ win15_kernel(const uint8_t *sbox_in, const uint16_t *xy_in, uint8_t *ks_out, uin
     }
 }
 
+// modes 20-27: variants X, U, K, their combinations and the loop before them (tools/ubench/win_var4.hpp)
+// on the same harness as v6.
+template <int MODE>
+__global__ void __launch_bounds__(64)
+win4v_kernel(const uint8_t *sbox_in, const uint16_t *xy_in, uint8_t *ks_out, uint8_t *sbox_out,
+             uint16_t *xy_out, uint64_t *cyc, uint32_t *wins, int nstreams, int N)
+{
+    constexpr int W = 16, SPW = 4;
+    __shared__ __attribute__((aligned(1024))) uint32_t Mk[SPW * 256];
+    __shared__ __attribute__((aligned(MAXN))) uint8_t Ring[SPW * MAXN];
+    __shared__ __attribute__((aligned(512))) uint8_t Sb[SPW * 512];
+    const uint32_t lane = threadIdx.x, l = lane % W, g = lane / W;
+    const int s = blockIdx.x * SPW + (int)g;
+    const bool live = s < nstreams;
+    uint8_t *S = Sb + g * 512;
+    uint32_t *M = Mk + g * 256;
+    uint8_t *R = Ring + g * MAXN;
+    for (int k = 0; k < 256 / W; ++k) {
+        const uint8_t v = live ? sbox_in[(size_t)s * 256 + l * (256 / W) + k] : 0;
+        S[l * (256 / W) + k] = v;
+        S[256 + l * (256 / W) + k] = v;
+        M[l * (256 / W) + k] = 0;
+    }
+    const uint32_t sxy = live ? xy_in[s] : 0;
+    __syncthreads();
+    zrc4::WinLane w{((sxy & 0xFFu) + 1u) & 0xFFu, sxy >> 8, (1u << 8) | (255u - l), l};
+    const uint64_t t0 = __builtin_amdgcn_s_memtime();
+    zrc4::win_windows_v4<MODE>(w, live ? (uint32_t)N : 0u, l, (uint32_t)(uintptr_t)S, (uint32_t)(uintptr_t)M,
+                               (uint32_t)(uintptr_t)R);
+    const uint64_t t1 = __builtin_amdgcn_s_memtime();
+    __syncthreads();
+    if (live) {
+        for (int k = 0; k < N / W; ++k) ks_out[(size_t)s * N + l * (N / W) + k] = R[l * (N / W) + k];
+        for (int k = 0; k < 256 / W; ++k) sbox_out[(size_t)s * 256 + l * (256 / W) + k] = S[l * (256 / W) + k];
+        if (l == 0) {
+            xy_out[s] = (uint16_t)(((w.xa - 1) & 255) | ((w.y & 255) << 8));
+            cyc[s] = t1 - t0;
+            wins[s] = (w.v >> 8) - 1;
+        }
+    }
+}
+
 // v7: one stream per wave, W = 64 (zrc4::win64_windows).
 __global__ void __launch_bounds__(64)
 win7_kernel(const uint8_t *sbox_in, const uint16_t *xy_in, uint8_t *ks_out, uint8_t *sbox_out,
@@ -1008,7 +1051,8 @@ static void run(int ns, int N, int reps)
     std::vector<float> ms;
     for (int r = 0; r < reps; ++r) {
         CHECK(hipEventRecord(e0));
-        if constexpr (V3 == 19) win19_kernel<<<(ns + 3) / 4, 64>>>(dsb, dxy, dks, dsbo, dxyo, dcyc, dwin, ns, N);
+        if constexpr (V3 >= 20 && V3 <= 27) win4v_kernel<V3><<<(ns + 3) / 4, 64>>>(dsb, dxy, dks, dsbo, dxyo, dcyc, dwin, ns, N);
+        else if constexpr (V3 == 19) win19_kernel<<<(ns + 3) / 4, 64>>>(dsb, dxy, dks, dsbo, dxyo, dcyc, dwin, ns, N);
         else if constexpr (V3 == 18) win18_kernel<<<(ns + 3) / 4, 64>>>(dsb, dxy, dks, dsbo, dxyo, dcyc, dwin, ns, N);
         else if constexpr (V3 == 17) win17_kernel<<<(ns + 3) / 4, 64>>>(dsb, dxy, dks, dsbo, dxyo, dcyc, dwin, ns, N);
         else if constexpr (V3 == 16) win16_kernel<<<(ns + 3) / 4, 64>>>(dsb, dxy, dks, dsbo, dxyo, dcyc, dwin, ns, N);
@@ -1056,15 +1100,17 @@ static void run(int ns, int N, int reps)
     (void)hipFree(dsb); (void)hipFree(dsbo); (void)hipFree(dks); (void)hipFree(dxy); (void)hipFree(dxyo); (void)hipFree(dcyc); (void)hipFree(dwin);
 }
 
-int main(int argc, char **argv)
+static void run_mode(int v3, int ns, int N, int w, int wpb)
 {
-    const int ns = argc > 1 ? atoi(argv[1]) : 4096;
-    const int N = argc > 2 ? atoi(argv[2]) : 1024;
-    const int w = argc > 3 ? atoi(argv[3]) : 16;
-    const int wpb = argc > 4 ? atoi(argv[4]) : 1;
-    if (N > MAXN || N % 16) { printf("bytes must be a multiple of 16 and <= %d\n", MAXN); return 1; }
-    const int v3 = argc > 5 ? atoi(argv[5]) : 1;
-    if (v3 == 19) run<16, 1, 19>(ns, N, 20);
+    if (v3 == 27) run<16, 1, 27>(ns, N, 20);
+    else if (v3 == 26) run<16, 1, 26>(ns, N, 20);
+    else if (v3 == 25) run<16, 1, 25>(ns, N, 20);
+    else if (v3 == 24) run<16, 1, 24>(ns, N, 20);
+    else if (v3 == 23) run<16, 1, 23>(ns, N, 20);
+    else if (v3 == 22) run<16, 1, 22>(ns, N, 20);
+    else if (v3 == 21) run<16, 1, 21>(ns, N, 20);
+    else if (v3 == 20) run<16, 1, 20>(ns, N, 20);
+    else if (v3 == 19) run<16, 1, 19>(ns, N, 20);
     else if (v3 == 18) run<16, 1, 18>(ns, N, 20);
     else if (v3 == 17) run<16, 1, 17>(ns, N, 20);
     else if (v3 == 16) run<16, 1, 16>(ns, N, 20);
@@ -1081,5 +1127,24 @@ int main(int argc, char **argv)
     else if (v3) { if (w == 8) run<8, 1, 1>(ns, N, 20); else if (wpb == 1) run<16, 1, 1>(ns, N, 20); else run<16, 2, 1>(ns, N, 20); }
     else if (w == 8) { if (wpb == 1) run<8, 1, 0>(ns, N, 20); else run<8, 2, 0>(ns, N, 20); }
     else { if (wpb == 1) run<16, 1, 0>(ns, N, 20); else run<16, 2, 0>(ns, N, 20); }
+}
+
+int main(int argc, char **argv)
+{
+    const int ns = argc > 1 ? atoi(argv[1]) : 4096;
+    const int N = argc > 2 ? atoi(argv[2]) : 1024;
+    const int w = argc > 3 ? atoi(argv[3]) : 16;
+    const int wpb = argc > 4 ? atoi(argv[4]) : 1;
+    if (N > MAXN || N % 16) { printf("bytes must be a multiple of 16 and <= %d\n", MAXN); return 1; }
+    // mode: one number, or a comma list run in order in this process (A/B
+    // against mode 6 under the same clocks)
+    const char *modes = argc > 5 ? argv[5] : "1";
+    for (const char *p = modes; *p;) {
+        char *end;
+        const int v3 = (int)strtol(p, &end, 10);
+        if (end == p) { printf("bad mode list %s\n", modes); return 1; }
+        run_mode(v3, ns, N, w, wpb);
+        p = *end == ',' ? end + 1 : end;
+    }
     return 0;
 }

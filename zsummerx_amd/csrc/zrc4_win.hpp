@@ -60,27 +60,56 @@ struct WinLane {
 // Windows until every stream of the wave has consumed `rem` bytes (rem is per
 // lane, equal inside a stream's 16 lanes; 0 = idle).  One asm statement; the
 // loop is rotated so that window n+1's read leaves right behind window n's
-// commit writes.  Per iteration n (a_l of window n already in flight):
+// commit writes, and it runs two windows per trip: the window is written
+// once (ZW_WINDOW) over the register that holds this window's &S[i_l] and the
+// one that receives window n+1's, and instantiated as (v106, v131) and
+// (v131, v106), so no copy of the address is needed and the backward branch
+// is taken once per two windows.  The first half leaves for the drain when
+// every stream is done (a forward branch, taken on exit only); the drain
+// serves both exits, because everything it reads (v120-v125, s[44:47]) lives
+// in the same register in both halves.
+//
+// Precondition: exec is all 64 lanes on entry (exec is restored with
+// s_mov_b64 exec, -1, not saved).  The workgroup is 64 threads; every return
+// ahead of the call in crypt_win_kernel is wave-uniform (an idle column or
+// bucket by ballot, a refused bucket by a flag every lane reads from LDS, a
+// lost claim by readfirstlane); the chunk loop around the call is
+// ballot-uniform; idle streams and streams past their end come in with
+// rem = 0, not with their lanes off.  tools/ubench's kernels call it from
+// straight-line code with rem = 0 for streams past the batch.
+//
+// Per window n (a_l of window n already in flight):
 //   1. two DPP chains interleaved step for step, so neither needs an s_nop:
 //      the inclusive scan of a over the stream's 16 lanes (row_shr 1, 2, 4,
 //      8: J_l = y + a_0 + .. + a_l; step 1 reads the a_l load directly, zero
 //      at row starts) and window n-1's y' = J of its last committed lane (max
 //      over the 16 lanes of (l + 1) << 8 | J, else the old y); window n-1's
 //      keystream select (S_final if a committed step <= l wrote t, else S0)
-//      in the last slots;
+//      in the last slots; J = scan + y' as an SDWA byte write (no mask);
 //   2. b_l = S0[J_l] and the marker max / read-back issue, window n-1's ring
-//      store behind them (not waited for); under that round trip the d rule (one-hot of med3(d, l, 16), none when d == l), the
-//      rem cap (bit min(rem, 16)) and the same one-hot plus bit l for a
-//      duplicate j;
+//      store behind them under exec = its commit mask (not waited for);
+//      under that round trip d as an SDWA byte write, the d rule (one-hot of
+//      med3(d, l, 16), none when d == l), the rem cap (bit min(rem, 16)) and
+//      the same one-hot plus bit l for a duplicate j;
 //   3. the duplicate-j rule (a select), DPP OR over the 16 lanes with the
-//      keystream address work and S0[t] read in the DPP wait slots, cut =
-//      lowest bit, window n+1's a_l address = this one's plus cut (SDWA byte
-//      add into the base register);
-//   4. commit (2 byte writes) under exec = lanes < cut, window n+1's a_l
-//      read, S_final[t] and marker(t) reads, then x, rem, the ring position
-//      and the commit mask under that round trip.
-// Every DPP read of a VGPR sits at least two VALU ops (or an s_nop) after the
-// VALU write of it.  Pinned temporaries v106-v131, s[40:47].
+//      keystream address work (t and e = t - x - 1 as SDWA byte writes), the
+//      y' candidate, the ring slot and the S0[t] read in the DPP wait slots
+//      (one s_nop 0 where nothing is left to put), cut = lowest bit, window
+//      n+1's a_l address = this one's plus cut (SDWA byte add from one
+//      address register into the other);
+//   4. commit (2 byte writes) under exec = lanes < cut (v_cmp_lt_u32_e64
+//      straight into the commit mask s[46:47]), window n+1's a_l read,
+//      S_final[t] and marker(t) reads, then y', x (SDWA byte write), rem and
+//      the ring position under that round trip.
+// Every DPP read of a VGPR sits at least two VALU ops (or a VALU op and an
+// s_nop) after the VALU write of it, and every SDWA dst_sel:BYTE_0 write has
+// a VALU op between it and its first reader (forwarded to the very next op
+// the value arrives without the byte select).  The lgkmcnt(1) in the middle
+// leaves the ring store in flight; the lgkmcnt(0) at the top of either half
+// drains the three reads of step 4 (on the first trip, the preamble's one).
+// Pinned temporaries v106, v107, v112, v114-v126, v128-v131 (v106 / v131:
+// the two address registers, S base in bytes 1-3; v129 also the d rule's
+// temporary), s[42:47].
 // (v_dot4_u32_u8 prefix sums over the window bytes were tried: the dot4
 // accumulator chain read stale values on MI355X -- bit-exact only because the
 // wrong j always tripped the duplicate rule -- and the DPP scan needs no
@@ -88,6 +117,79 @@ struct WinLane {
 #define ZW_ADDR(XA)                                                                               \
     "v_add_u32_sdwa v106, " XA ", %[l] dst_sel:BYTE_0 dst_unused:UNUSED_PRESERVE src0_sel:DWORD "  \
     "src1_sel:DWORD\n\t"
+#define ZW_BYTE0 " dst_sel:BYTE_0 dst_unused:UNUSED_PAD src0_sel:DWORD "
+// window n-1's ring store (also the drain's)
+#define ZW_RING                                                                                    \
+    "s_mov_b64 exec, s[46:47]\n\t"                                                                 \
+    "ds_write_b8 v125, v124\n\t"                                                                   \
+    "s_mov_b64 exec, -1\n\t"
+// A: &S[i_l] of this window, N: receives window n+1's
+#define ZW_WINDOW(A, N)                                                                            \
+    /* 1. scan of a, tail of window n-1 */                                                         \
+    "s_waitcnt lgkmcnt(0)\n\t"                                                                     \
+    "v_add_u32_dpp v112, v107, v107 row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"         \
+    "v_max_u32_dpp v120, v120, v120 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"            \
+    "v_cmp_ge_u32_e64 s[42:43], v123, %[v]\n\t"                                                    \
+    "v_add_u32_dpp v112, v112, v112 row_shr:2 row_mask:0xf bank_mask:0xf\n\t"                      \
+    "v_max_u32_dpp v120, v120, v120 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"            \
+    "v_add_u32 %[v], 0x100, %[v]\n\t"                                                              \
+    "v_add_u32_dpp v112, v112, v112 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"                      \
+    "v_max_u32_dpp v120, v120, v120 row_half_mirror row_mask:0xf bank_mask:0xf\n\t"                \
+    "s_or_b64 s[42:43], s[42:43], s[44:45]\n\t"                                                    \
+    "v_cndmask_b32_e64 v124, v121, v122, s[42:43]\n\t"                                             \
+    "v_add_u32_dpp v112, v112, v112 row_shr:8 row_mask:0xf bank_mask:0xf\n\t"                      \
+    "v_max_u32_dpp v120, v120, v120 row_mirror row_mask:0xf bank_mask:0xf\n\t"                     \
+    "v_add_u32_sdwa v112, v112, v120" ZW_BYTE0 "src1_sel:BYTE_0\n\t"   /* J = scan + y' (mod 256) */ \
+    /* 2. b / marker round trip, d rule and rem cap under it */                                    \
+    "v_and_b32 %[y], 0xff, v120\n\t"                         /* (between the byte write and its readers) */ \
+    "v_add_u32 v114, %[sb], v112\n\t"                                                              \
+    "v_lshl_add_u32 v115, v112, 2, %[mb]\n\t"                                                      \
+    "ds_read_u8 v116, v114\n\t"                              /* b_l = S0[J] */                     \
+    "ds_max_u32 v115, %[v]\n\t"                                                                    \
+    "ds_read_b32 v117, v115\n\t"                             /* lowest lane with this J */         \
+    ZW_RING                                                  /* behind the round trip */           \
+    "v_sub_u32_sdwa v118, v112, %[xa]" ZW_BYTE0 "src1_sel:DWORD\n\t"   /* d */                     \
+    "v_min_u32 v119, 16, %[rem]\n\t"                         /* (between) */                       \
+    "v_med3_u32 v129, v118, %[l], 16\n\t"                                                          \
+    "v_cmp_ne_u32 vcc, v118, %[l]\n\t"                                                             \
+    "v_cndmask_b32 v129, 16, v129, vcc\n\t"                                                        \
+    "v_lshlrev_b32 v118, v129, 1\n\t"                        /* bit 16 = no d conflict */          \
+    "v_lshlrev_b32 v119, v119, 1\n\t"                                                              \
+    "v_or_b32 v118, v118, v119\n\t"                          /* + bit min(rem, 16): cut <= rem */  \
+    "v_or_b32 v119, v118, %[bitl]\n\t"                       /* the same if this lane's J repeats */ \
+    "s_waitcnt lgkmcnt(1)\n\t"                                                                     \
+    /* 3. duplicate-J rule, OR over the stream's 16 lanes, cut */                                  \
+    "v_cmp_ne_u32 vcc, v117, %[v]\n\t"                                                             \
+    "v_cndmask_b32 v118, v118, v119, vcc\n\t"                                                      \
+    "v_add_u32_sdwa v126, v107, v116 dst_sel:BYTE_0 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD\n\t" /* &S[t] */ \
+    "v_add_u32_sdwa v128, v107, v116" ZW_BYTE0 "src1_sel:DWORD\n\t"    /* t */                     \
+    "ds_read_u8 v121, v126\n\t"                              /* S0[t] */                           \
+    "v_or_b32_dpp v118, v118, v118 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"             \
+    "v_or_b32 v130, %[l1], v112\n\t"                         /* y' candidate of this lane */       \
+    "v_sub_u32_sdwa v119, v128, %[xa]" ZW_BYTE0 "src1_sel:DWORD\n\t"   /* e = t - x - 1 */         \
+    "v_or_b32_dpp v118, v118, v118 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"             \
+    "v_lshl_add_u32 v129, v128, 2, %[mb]\n\t"                                                      \
+    "v_bfi_b32 v125, %[rmask], %[rp], %[rb]\n\t"             /* ring slot of this lane */          \
+    "v_or_b32_dpp v118, v118, v118 row_half_mirror row_mask:0xf bank_mask:0xf\n\t"                 \
+    "v_cmp_le_u32_e64 s[44:45], v119, %[l]\n\t"              /* t is the i of a step <= l */       \
+    "s_nop 0\n\t"                                                                                  \
+    "v_or_b32_dpp v118, v118, v118 row_mirror row_mask:0xf bank_mask:0xf\n\t"                      \
+    "v_ffbl_b32 v118, v118\n\t"                              /* cut */                             \
+    "v_cmp_lt_u32_e64 s[46:47], %[l], v118\n\t"              /* commit mask (ring store next window) */ \
+    "v_add_u32_sdwa " N ", " A ", v118 dst_sel:BYTE_0 dst_unused:UNUSED_PRESERVE src0_sel:BYTE_0 src1_sel:DWORD\n\t" /* window n+1's a_l address */ \
+    /* 4. commit, then window n+1's read right behind it */                                        \
+    "s_mov_b64 exec, s[46:47]\n\t"                                                                 \
+    "ds_write_b8 " A ", v116\n\t"                            /* S[i_l] = b_l */                    \
+    "ds_write_b8 v114, v107\n\t"                             /* S[J_l] = a_l */                    \
+    "s_mov_b64 exec, -1\n\t"                                                                       \
+    "ds_read_u8 v107, " N "\n\t"                             /* a_l of window n+1 */               \
+    "ds_read_u8 v122, v126\n\t"                              /* S_final[t] */                      \
+    "ds_read_b32 v123, v129\n\t"                             /* lowest lane whose J == t */        \
+    "v_cndmask_b32_e64 v120, %[y], v130, s[46:47]\n\t"                                             \
+    "v_add_u32_sdwa %[xa], %[xa], v118" ZW_BYTE0 "src1_sel:DWORD\n\t"                              \
+    "v_sub_u32 %[rem], %[rem], v118\n\t"                                                           \
+    "v_add_u32 %[rp], %[rp], v118\n\t"                                                             \
+    "v_cmp_ne_u32 vcc, 0, %[rem]\n\t"
 __device__ __forceinline__ void win_windows(WinLane &w, uint32_t rem, uint32_t l, uint32_t sb, uint32_t mb,
                                             uint32_t rb)
 {
@@ -98,86 +200,17 @@ __device__ __forceinline__ void win_windows(WinLane &w, uint32_t rem, uint32_t l
         "s_mov_b64 s[44:45], 0\n\t"
         "v_mov_b32 v123, 0\n\t"
         "v_mov_b32 v106, %[sb]\n\t"                              // S base (256-aligned) in bytes 1-3
+        "v_mov_b32 v131, %[sb]\n\t"
         "v_mov_b32 v126, %[sb]\n\t"
         ZW_ADDR("%[xa]")
         "ds_read_u8 v107, v106\n\t"                             // a_l of window 0
         "ZW_LOOP_%=:\n\t"
-        // 1. scan of a, tail of window n-1
-        "s_waitcnt lgkmcnt(0)\n\t"
-        "v_add_u32_dpp v112, v107, v107 row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
-        "v_max_u32_dpp v120, v120, v120 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-        "v_cmp_ge_u32_e64 s[42:43], v123, %[v]\n\t"
-        "v_add_u32_dpp v112, v112, v112 row_shr:2 row_mask:0xf bank_mask:0xf\n\t"
-        "v_max_u32_dpp v120, v120, v120 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_u32 %[v], 0x100, %[v]\n\t"
-        "v_add_u32_dpp v112, v112, v112 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
-        "v_max_u32_dpp v120, v120, v120 row_half_mirror row_mask:0xf bank_mask:0xf\n\t"
-        "s_or_b64 s[42:43], s[42:43], s[44:45]\n\t"
-        "v_cndmask_b32_e64 v124, v121, v122, s[42:43]\n\t"
-        "v_add_u32_dpp v112, v112, v112 row_shr:8 row_mask:0xf bank_mask:0xf\n\t"
-        "v_max_u32_dpp v120, v120, v120 row_mirror row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_u32 v112, v112, v120\n\t"                       // + y' (byte 0 of v120; J is masked below)
-        // 2. b / marker round trip, d rule and rem cap under it
-        "v_add_u32_sdwa v114, %[sb], v112 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0\n\t"
-        "v_and_b32 v112, 0xff, v112\n\t"                       // J
-        "v_lshl_add_u32 v115, v112, 2, %[mb]\n\t"
-        "ds_read_u8 v116, v114\n\t"                             // b_l = S0[J]
-        "ds_max_u32 v115, %[v]\n\t"
-        "ds_read_b32 v117, v115\n\t"                            // lowest lane with this J
-        "s_mov_b64 s[40:41], exec\n\t"
-        "s_mov_b64 exec, s[46:47]\n\t"
-        "ds_write_b8 v125, v124\n\t"                            // window n-1's ring store, behind the round trip
-        "s_mov_b64 exec, s[40:41]\n\t"
-        "v_and_b32 %[y], 0xff, v120\n\t"
-        "v_sub_u32 v118, v112, %[xa]\n\t"
-        "v_and_b32 v118, 0xff, v118\n\t"                       // d
-        "v_med3_u32 v119, v118, %[l], 16\n\t"
-        "v_cmp_ne_u32 vcc, v118, %[l]\n\t"
-        "v_cndmask_b32 v119, 16, v119, vcc\n\t"
-        "v_lshlrev_b32 v118, v119, 1\n\t"                       // bit 16 = no d conflict
-        "v_min_u32 v119, 16, %[rem]\n\t"
-        "v_lshlrev_b32 v119, v119, 1\n\t"
-        "v_or_b32 v118, v118, v119\n\t"                        // + bit min(rem, 16): cut <= rem
-        "v_or_b32 v119, v118, %[bitl]\n\t"                     // the same if this lane's J repeats
-        "v_or_b32 v130, %[l1], v112\n\t"                        // y' candidate of this lane
-        "v_bfi_b32 v125, %[rmask], %[rp], %[rb]\n\t"            // ring slot of this lane
-        "s_waitcnt lgkmcnt(1)\n\t"
-        // 3. duplicate-J rule, OR over the stream's 16 lanes, cut
-        "v_cmp_ne_u32 vcc, v117, %[v]\n\t"
-        "v_cndmask_b32 v118, v118, v119, vcc\n\t"
-        "v_add_u32_sdwa v126, v107, v116 dst_sel:BYTE_0 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD\n\t"   // &S[t]
-        "v_add_u32 v128, v107, v116\n\t"
-        "ds_read_u8 v121, v126\n\t"                             // S0[t]
-        "v_or_b32_dpp v118, v118, v118 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-        "v_sub_u32 v131, v128, %[xa]\n\t"
-        "v_and_b32 v128, 0xff, v128\n\t"                       // t
-        "v_or_b32_dpp v118, v118, v118 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-        "v_and_b32 v131, 0xff, v131\n\t"                       // e = t - x - 1
-        "v_lshl_add_u32 v129, v128, 2, %[mb]\n\t"
-        "v_or_b32_dpp v118, v118, v118 row_half_mirror row_mask:0xf bank_mask:0xf\n\t"
-        "v_cmp_le_u32_e64 s[44:45], v131, %[l]\n\t"             // t is the i of a step <= l
-        "v_mov_b32 v131, v106\n\t"                              // &S[i_l] of window n
-        "v_or_b32_dpp v118, v118, v118 row_mirror row_mask:0xf bank_mask:0xf\n\t"
-        "v_ffbl_b32 v118, v118\n\t"                             // cut
-        "v_cmp_lt_u32 vcc, %[l], v118\n\t"
-        "v_add_u32_sdwa v106, v106, v118 dst_sel:BYTE_0 dst_unused:UNUSED_PRESERVE src0_sel:BYTE_0 src1_sel:DWORD\n\t"   // window n+1's a_l address
-        // 4. commit, then window n+1's read right behind it
-        "s_and_saveexec_b64 s[40:41], vcc\n\t"
-        "ds_write_b8 v131, v116\n\t"                            // S[i_l] = b_l
-        "ds_write_b8 v114, v107\n\t"                            // S[J_l] = a_l
-        "s_mov_b64 exec, s[40:41]\n\t"
-        "ds_read_u8 v107, v106\n\t"                             // a_l of window n+1
-        "ds_read_u8 v122, v126\n\t"                             // S_final[t]
-        "ds_read_b32 v123, v129\n\t"                            // lowest lane whose J == t
-        "s_and_b64 s[46:47], vcc, s[40:41]\n\t"                 // commit mask (ring store next iteration)
-        "v_cndmask_b32 v120, %[y], v130, vcc\n\t"
-        "v_add_u32 %[xa], %[xa], v118\n\t"
-        "v_and_b32 %[xa], 0xff, %[xa]\n\t"
-        "v_sub_u32 %[rem], %[rem], v118\n\t"
-        "v_add_u32 %[rp], %[rp], v118\n\t"
-        "v_cmp_ne_u32 vcc, 0, %[rem]\n\t"
+        ZW_WINDOW("v106", "v131")
+        "s_cbranch_vccz ZW_DRAIN_%=\n\t"                        // taken on exit only
+        ZW_WINDOW("v131", "v106")
         "s_cbranch_vccnz ZW_LOOP_%=\n\t"
         // drain: tail of the last window (window n's read is harmless)
+        "ZW_DRAIN_%=:\n\t"
         "s_waitcnt lgkmcnt(0)\n\t"
         "v_max_u32_dpp v120, v120, v120 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
         "v_cmp_ge_u32_e64 s[42:43], v123, %[v]\n\t"
@@ -188,18 +221,15 @@ __device__ __forceinline__ void win_windows(WinLane &w, uint32_t rem, uint32_t l
         "v_max_u32_dpp v120, v120, v120 row_half_mirror row_mask:0xf bank_mask:0xf\n\t"
         "s_nop 1\n\t"
         "v_max_u32_dpp v120, v120, v120 row_mirror row_mask:0xf bank_mask:0xf\n\t"
-        "s_mov_b64 s[40:41], exec\n\t"
-        "s_mov_b64 exec, s[46:47]\n\t"
-        "ds_write_b8 v125, v124\n\t"
-        "s_mov_b64 exec, s[40:41]\n\t"
+        ZW_RING
         "v_and_b32 %[y], 0xff, v120\n\t"
         "s_waitcnt lgkmcnt(0)\n\t"
         : [xa] "+v"(w.xa), [y] "+v"(w.y), [v] "+v"(w.v), [rem] "+v"(rem), [rp] "+v"(w.rp)
         : [l] "v"(l), [sb] "v"(sb), [mb] "v"(mb), [rb] "v"(rb), [bitl] "v"(bitl), [l1] "v"(l1),
           [rmask] "s"(kWinRing - 1)
         : "memory", "vcc", "scc", "v106", "v107", "v112", "v114", "v115", "v116", "v117", "v118", "v119", "v120",
-          "v121", "v122", "v123", "v124", "v125", "v126", "v128", "v129", "v130", "v131", "s40", "s41",
-          "s42", "s43", "s44", "s45", "s46", "s47");
+          "v121", "v122", "v123", "v124", "v125", "v126", "v128", "v129", "v130", "v131", "s42", "s43",
+          "s44", "s45", "s46", "s47");
 }
 
 // Declared bucket groups of a grouped window launch (zrc4_crypt_grouped_declared):
